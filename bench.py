@@ -13,6 +13,13 @@ roofline: the dominant kernel's algorithmic bytes per launch (packets x
         (2L + T): read L, write L + T, or read L + T, write L) over its
         average launch time, timed with HIP events on the launch stream.
 
+A plain run sets up, warms up, times --steps steps and prints the line
+(ms_per_step: one timed step).  --full adds what is checked or measured
+beside them: the round trip against the plaintext, config 5's shards
+against the reference's digests, the reference on the host cores
+(cpu_baseline).  --dump-outputs DIR writes what the last timed step
+returned; the inputs are the same bytes on every run.
+
 Multi-GPU (config 5): one process per GPU, rank r protects/unprotects its
 contiguous 1M-packet shard of one 8M-packet stream, continuing the
 stream state exactly where rank r-1's shard ends (srtp_stream_import).
@@ -301,6 +308,50 @@ def shard_check(args, cfg_id, rank, n, K, use_dev, plain, make_sessions,
     return not bad
 
 
+DUMP_SLOTS = 4096        # packet slots of the arena a dump keeps
+DUMP_PACKETS = 1 << 20   # packets whose pos / end / err it keeps
+
+
+def dump_outputs(path, prefix, arena, slot, arrays):
+    """--dump-outputs: what the last timed step handed back to its caller,
+    as .npy files two builds can be compared by.  A step protects and
+    unprotects in place, so the arena holds each packet's plaintext again
+    and, past its end, the authentication tag protect computed over the
+    ciphertext; pos / end are the windows as the two calls left them, err
+    the per-packet results of either call.  The arena is 1.2 GB as bytes:
+    DUMP_SLOTS whole slots are kept, picked by a fixed seed; the per-packet
+    arrays are whole up to DUMP_PACKETS packets (a seeded sample above).
+    About 55 MB at the most (1416-B slots)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = arena.numel() // slot
+    rng = np.random.default_rng(20240229)
+    pick = lambda m: np.arange(n) if n <= m else \
+        np.sort(rng.choice(n, m, replace=False))
+    slots, pkts = pick(DUMP_SLOTS), pick(DUMP_PACKETS)
+
+    def save(name, a, dtype):
+        np.save(os.path.join(path, prefix + name + ".npy"),
+                np.ascontiguousarray(a, dtype=dtype))
+
+    def host(a, idx, dtype):
+        if isinstance(a, torch.Tensor):
+            a = a[torch.from_numpy(idx).to(a.device)].cpu().numpy()
+        else:
+            a = np.asarray(a)[idx]
+        return a.view(dtype)
+
+    save("slot_index", slots, np.float64)
+    save("arena_slots", host(arena.view(n, slot), slots, np.uint8),
+         np.float32)
+    save("packet_index", pkts, np.float64)
+    for name, a, dt in zip(("pos", "end", "err_protect", "err_unprotect"),
+                           arrays, (np.uint32, np.uint32, np.int32,
+                                    np.int32)):
+        save(name, host(a, pkts, dt),
+             np.float64 if dt is np.uint32 else np.float32)
+
+
 def dry_run(args, world, rank):
     """--dry-run (CPU, testing the launcher): the rank plumbing of the
     sharded run without a GPU -- gloo rendezvous, this rank's shard of the
@@ -371,8 +422,22 @@ def main():
                          "when --gpus > 1")
     ap.add_argument("--packets", type=int, default=None,
                     help="override packets per GPU (testing only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the round trip verified "
+                         "against the plaintext, config 5's shards against "
+                         "the reference's digests, and the reference on the "
+                         "host cores (cpu_baseline); a run without it sets "
+                         "up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-verify", action="store_true",
+                    help="--full without the round-trip and shard checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step "
+                         "returned to its caller as DIR/<name>.npy (float32 "
+                         "/ float64): the packet slots of a fixed sample of "
+                         "packets, and every packet's pos, end and the two "
+                         "err arrays")
     ap.add_argument("--e2e", action="store_true",
                     help="end-to-end: packets start and end in pinned host "
                          "memory (H2D + protect + D2H, H2D + unprotect + "
@@ -564,7 +629,7 @@ def main():
         ("srtp_encrypt", "srtp_decrypt")
     log("workload built (%d packets)" % n)
     arena = torch.from_numpy(arena_h).to(dev)
-    plain = arena.clone() if not args.no_verify else None
+    plain = arena.clone() if args.full and not args.no_verify else None
     klen = P.key_len(suite) + P.salt_len(suite)
     keys = W.make_keys(nsess, klen, ids=key_ids)
     # one explicit stream for the whole run (torch copies and the library
@@ -851,6 +916,16 @@ def main():
                             dtype=torch.float64, device=dev)
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     log("timed steps done")
+    if args.dump_outputs:
+        k = args.steps - 1
+        assert k >= 0, "--dump-outputs: no timed step ran"
+        dump_outputs(args.dump_outputs, "" if world == 1 else
+                     "rank%d_" % rank, arena, int(cap[0] - pos[0]),
+                     (winp[k], wine[k], errbuf[0, k], errbuf[1, k])
+                     if use_dev and not args.e2e else
+                     (p_d, e_d, errbuf[0, k], errbuf[1, k]) if use_dev else
+                     (p, e, err_e, err_d))
+        log("outputs written")
     if os.environ.get("BENCH_WATCHDOG"):
         import faulthandler
         faulthandler.dump_traceback_later(
@@ -875,8 +950,8 @@ def main():
         bad = int(torch.count_nonzero((a2 != p2) & win).item())
         verified = bad == 0 and tot_err == 0
         del win, a2, p2
+        log("verified")
 
-    log("verified")
     for tx, rx in sess_objs:
         for s in tx + rx:
             s.close()
@@ -1029,7 +1104,7 @@ def main():
         if shards_checked else None,
         "roofline": roof,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(cfg, args.rtcp)
     print(json.dumps(line))
     if world > 1:

@@ -1,5 +1,6 @@
 #!/bin/bash
 # One GPU-box pass: parity tests, smoke, bench, kernel-trace profile.
+# BENCH_ARGS=--full: the bench line verified and beside the CPU baseline.
 # Each GPU step has its own time limit; the first failure ends the script.
 set -o pipefail
 mkdir -p gpurun_out

@@ -10,5 +10,5 @@ fi
 IFS=';' read -ra BS <<< "${BENCHES:-}"
 for nb in "${BS[@]}"; do
   n=${nb%%=*}; a=${nb#*=}
-  timeout -k 10 300 python bench.py --no-cpu-baseline $a > $O/$n.json 2> $O/$n.err || exit $?
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline $a > $O/$n.json 2> $O/$n.err || exit $?
 done

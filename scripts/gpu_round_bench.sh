@@ -8,7 +8,7 @@ O=gpurun_out/round
 mkdir -p $O
 b() {   # name, bench args...
   local n=$1; shift
-  timeout -k 10 300 python bench.py "$@" > $O/$n.json 2> $O/$n.err || exit $?
+  timeout -k 10 300 python bench.py --full "$@" > $O/$n.json 2> $O/$n.err || exit $?
 }
 b c2
 b c3 --config 3

@@ -3,6 +3,8 @@
 # "run"):
 #   TESTS="file::test ..."        pytest -m gpu of those, tests.log
 #   BENCHES="name=args;..."       bench.py lines, name.json / name.err
+#                                 (--full among the args: the verified
+#                                 line beside the CPU baseline)
 #   TRACES="name=args;..."        rocprofv3 --kernel-trace --stats of a
 #                                 bench.py run: trace_name/ (csv) + name.json
 # Every GPU step runs under its own time limit; the first failure ends it.

@@ -214,7 +214,7 @@ def test_bench_spawns_two_gpu_ranks():
                         "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"),
                         "--gpus", "2", "--same-device", "--packets", "8192",
-                        "--steps", "2", "--warmup", "1",
+                        "--steps", "2", "--warmup", "1", "--full",
                         "--no-cpu-baseline"], capture_output=True, text=True,
                        env=env, timeout=180, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
