@@ -219,6 +219,28 @@ int srtp_rx_fold(struct srtp_stream_state *st, enum srtp_suite suite,
 		 const struct srtp_rx_rec *rec, size_t n, int32_t *err,
 		 size_t *ndone);
 
+/**
+ * The receive planner's rule on the host (no GPU needed): the index and
+ * replay verdict of every packet of ONE stream's batch that arrives
+ * reordered, duplicated or with gaps, computed the way the device planner
+ * computes it -- a (sum, max) scan over blocks of `block` packets, then per
+ * packet a verification with the reference receiver's own step
+ * (src/srtp/srtp.c:313-323, misc.c:22-41) and the replay verdict
+ * (replay.c:32-62) with a search of the `lookback` arrivals before it for a
+ * duplicate's original -- not a sequential walk.  seq[i]: the packets'
+ * sequence numbers in arrival order, every tag taken as authentic; st0: the
+ * stream before the batch (s_l_set == 0: a fresh stream).  *fail == 0: the
+ * batch is settled -- ix[i] is packet i's 48-bit index, err[i] its result
+ * (0 or EALREADY) and *st1 the stream after it, all exactly the sequential
+ * receiver's.  *fail != 0: the rule cannot settle it (for instance a
+ * packet from before a rollover arriving after it: ETIMEDOUT); *st1 = *st0,
+ * ix and err are unspecified.  block >= 1.  0, EINVAL or ENOMEM.
+ */
+int srtp_rx_plan_host(const struct srtp_stream_state *st0, const uint16_t *seq,
+		      size_t n, uint32_t block, uint32_t lookback,
+		      uint64_t *ix, int32_t *err, struct srtp_stream_state *st1,
+		      uint32_t *fail);
+
 /** Batched session setup: n contexts in one GPU launch (key agility). */
 int srtp_alloc_many(struct srtp **srtpv, size_t n, enum srtp_suite suite,
 		    const uint8_t *keys, size_t key_bytes, int flags);
@@ -262,6 +284,9 @@ int srtp_alloc_many(struct srtp **srtpv, size_t n, enum srtp_suite suite,
  * planner launches, not the plan inside the crypto launch), "fzepoch"
  * (test hook, process-wide and one-shot: the next fused launch of any
  * thread takes this look-back epoch, its look-back words zeroed first),
+ * "norxplan" (a one-stream unprotect batch whose device plan was rejected
+ * for reordered or replayed packets goes straight to the host engine, not
+ * to the device receive planner),
  * "rxseq" (srtp_rx_index* and srtp_rx_fold walk
  * in one sequential pass, not in parallel parts), "freshmulti" (the
  * planner's first-batch hint: 1 sends a session's first batch to the
@@ -284,7 +309,10 @@ int srtp_gpu_tune(const char *name, long value);
  * packets they carried), "pcfused" (those of them that ran several
  * operations as one launch), "gated" (asynchronous calls queued behind one
  * the host completed, re-run when waited for), "freshmulti" (the
- * first-batch hint, 0/1).  0 for an unknown name.
+ * first-batch hint, 0/1), "rxplans" (reordered / duplicated one-stream
+ * unprotect batches completed by the device receive planner), "rxlate"
+ * (late packets it accepted), "rxdups" (EALREADY verdicts it gave).  0 for
+ * an unknown name.
  */
 uint64_t srtp_gpu_counter(const char *name);
 

@@ -93,6 +93,10 @@ static void tk_finish_one(void)
 			r = dev_mplanned_(k->op, k->sessv, k->nsess, &k->d, 1,
 					  &pf);
 		}
+		/* reordered or replayed arrivals: the receive planner */
+		else if (!r && t->kind == TK_PLANNED &&
+			 rx_eligible(k->op, k->sessv[0], k->pfail))
+			r = dev_rxplanned(k->sessv[0], &k->d, NULL, NULL, NULL);
 		else if (!r)
 			r = -1;
 		if (r == -1)
@@ -384,6 +388,9 @@ static int run_dev(int op, struct srtp **sessv, size_t nsess,
 			r = dev_planned(op, sessv[0], d, &pf);
 		if (r == -1 && (pf & SPF_SSRC))
 			r = dev_splanned(op, sessv[0], d);
+		/* reordered or replayed arrivals: the receive planner */
+		else if (r == -1 && rx_eligible(op, sessv[0], pf))
+			r = dev_rxplanned(sessv[0], d, NULL, NULL, NULL);
 		if (r >= 0)
 			return r;
 	}

@@ -22,6 +22,7 @@
 #include "re_srtp_batch.h"
 #include "re_rtcp_batch.h"
 #include "../srtpgpu.h"
+#include "../hip/plan_rx_rule.h"
 #include "fault.h"
 #include "pool.h"
 #include "srtp_int.h"
@@ -849,6 +850,271 @@ int dev_planned(int op, struct srtp *s, struct srtp_batch_dev *d,
 	err = dev_planned_finish(&k);
 	*pfail = k.pfail;
 	return err;
+}
+
+/* ---- one stream, reordered / duplicated arrivals (plan_rx.hip) -------- */
+
+/*
+ * The host twin of the device receive planner: the same rule
+ * (hip/plan_rx_rule.h) in the same decomposition -- aggregates of `block`
+ * packets, a scan of the aggregates, u[] / Mx[] per packet, the settle
+ * pass with its look-back across blocks -- so small block / lookback
+ * values exercise every boundary of plan_rx.hip on the CPU.
+ */
+int srtp_rx_plan_host(const struct srtp_stream_state *st0, const uint16_t *seq,
+		      size_t n, uint32_t block, uint32_t lookback,
+		      uint64_t *ix, int32_t *err, struct srtp_stream_state *st1,
+		      uint32_t *fail)
+{
+	const size_t nb = block ? (n + block - 1) / block : 0;
+	struct rx_agg *agg, total = rx_identity();
+	int64_t *u, *mx, H0, lix0, lix, Mn, u0 = 0;
+	uint64_t bitmap;
+	size_t b, i;
+	int bump = 0;
+
+	if (!st0 || !seq || !n || !block || !ix || !err || !st1 || !fail ||
+	    n > UINT32_MAX || (st0->replay_rtp_lix >> 62))
+		return EINVAL;
+	*st1 = *st0;
+	*fail = 0;
+	agg = fi_malloc(nb * sizeof(*agg));
+	u = fi_malloc(n * sizeof(*u));
+	mx = fi_malloc(n * sizeof(*mx));
+	if (!agg || !u || !mx) {
+		free(agg);
+		free(u);
+		free(mx);
+		return ENOMEM;
+	}
+	/* seed: a fresh stream takes seq[0] as s_l (stream_get_seq) */
+	H0 = (int64_t)(((uint64_t)st0->roc << 16) |
+		       (st0->s_l_set ? st0->s_l : seq[0]));
+	lix0 = (int64_t)st0->replay_rtp_lix;
+	if (rx_step(H0, seq[0], &u0, &bump)) {
+		*fail = SPF_TIMEOUT;
+		goto out;
+	}
+#define RX_ELEM(i) rx_elem((i) ? rx_sdiff16(seq[i], seq[(i) - 1]) : u0)
+	/* 1. per-block aggregates */
+	for (b = 0; b < nb; b++) {
+		struct rx_agg a = rx_identity();
+		for (i = b * block; i < (b + 1) * (size_t)block && i < n; i++)
+			a = rx_combine(a, RX_ELEM(i));
+		agg[b] = a;
+	}
+	/* 2. exclusive scan of the aggregates */
+	for (b = 0; b < nb; b++) {
+		const struct rx_agg a = agg[b];
+		agg[b] = total;
+		total = rx_combine(total, a);
+	}
+	/* 3. indices and exclusive prefix maxima, block by block */
+	for (b = 0; b < nb; b++) {
+		struct rx_agg run = agg[b];
+		for (i = b * block; i < (b + 1) * (size_t)block && i < n; i++) {
+			mx[i] = run.m;
+			run = rx_combine(run, RX_ELEM(i));
+			u[i] = run.s;
+		}
+	}
+#undef RX_ELEM
+	/* 4. settle; 5. the state after the batch */
+	Mn = rx_max(H0, total.m);
+	lix = rx_max(lix0, total.m);
+	bitmap = rx_bitmap_base(lix, lix0, st0->replay_rtp_bitmap);
+	for (i = 0; i < n; i++) {
+		const int r = rx_settle(u, mx, (uint32_t)i, seq[i], lookback, H0,
+					lix0, st0->replay_rtp_bitmap, 0);
+		if (r == RX_UNSETTLED) {
+			*fail = SPF_ORDER;
+			goto out;
+		}
+		ix[i] = (uint64_t)u[i];
+		err[i] = r == RX_DUP ? EALREADY : 0;
+		if (r == RX_OK)
+			bitmap |= rx_bit(lix, u[i]);
+	}
+	st1->roc = (uint32_t)((uint64_t)Mn >> 16);
+	st1->s_l = (uint16_t)((uint64_t)Mn & 0xffffu);
+	st1->s_l_set = 1;
+	st1->replay_rtp_lix = (uint64_t)lix;
+	st1->replay_rtp_bitmap = bitmap;
+ out:
+	free(agg);
+	free(u);
+	free(mx);
+	return 0;
+}
+
+/* a rejected one-stream unprotect plan the receive planner may settle:
+ * only the arrival order or a replayed index was in its way */
+int rx_eligible(int op, const struct srtp *s, uint32_t pfail)
+{
+	return op == OP_RTP_DEC && !g_env.norxplan && s->nstreams <= 1 &&
+	       pfail && !(pfail & ~(uint32_t)(SPF_ORDER | SPF_REPLAY));
+}
+
+/*
+ * One-stream unprotect batch behind such a rejection: sgpu_plan_rx, the
+ * general descriptor-driven crypto launches guarded by its verdict, the
+ * guarded results, one synchronisation.  hpos / hend / herr: host arrays
+ * the results are copied down to as well (host-window calls), or NULL.
+ * 0: done, the stream advanced; -1: not settled, or a forged packet
+ * (undone) -- nothing modified, the caller's fallback continues; errno.
+ */
+int dev_rxplanned(struct srtp *s, struct srtp_batch_dev *d, uint32_t *hpos,
+		  uint32_t *hend, int32_t *herr)
+{
+	const struct comp *c0 = &s->rtp;
+	const int gcm = c0->mode == SGPU_MODE_GCM;
+	const size_t n = d->n;
+	const uint32_t T = gcm ? 16u : c0->tag_len;
+	const size_t scr = sgpu_plan_rx_scratch((uint32_t)n);
+	const struct srtp_stream *st0 = s->nstreams ? &s->streams[0] : NULL;
+	struct sgpu_rxplan_in in;
+	struct sgpu_rxplan_out *ro, *ro_d;
+	struct sgpu_hdr *hd_d;
+	struct srtp_stream *st;
+	uint64_t *desc_d;
+	uint32_t *es_d, *save_d;
+	uint8_t *vd_d;
+	void *stream = d->stream;
+	struct ws *w = ws_get();
+	int err, q;
+
+	if (!w)
+		return ENOMEM;
+	/* the rule computes in signed 64 bits (an imported window) */
+	if (st0 && (st0->replay_rtp.lix >> 62))
+		return -1;
+	err = pool_reserve(w, &w->hd, n * sizeof(struct sgpu_hdr));
+	if (!err)
+		err = pool_reserve(w, &w->dsc, n * 8);
+	if (!err)
+		err = pool_reserve(w, &w->vs, n * 5 + 64);
+	if (!err)
+		err = pool_reserve(w, &w->cm, 4);
+	if (!err)
+		err = pool_reserve(w, &w->pl, 64 + sizeof(*ro));
+	if (!err)
+		err = pool_reserve(w, &w->es, n * 4);
+	if (!err)
+		err = pool_reserve(w, &w->mscr, scr);
+	if (!err && hpos)
+		err = pool_reserve(w, &w->ms, n * 12);
+	if (err)
+		return err;
+	hd_d = (struct sgpu_hdr *)w->hd.d;
+	desc_d = (uint64_t *)w->dsc.d;
+	save_d = (uint32_t *)(w->vs.d + 64);
+	vd_d = w->vs.d + 64 + n * 4;
+	ro = (struct sgpu_rxplan_out *)w->pl.h;
+	ro_d = (struct sgpu_rxplan_out *)w->pl.d;
+	es_d = (uint32_t *)w->es.d;
+
+	memset(&in, 0, sizeof(in));
+	in.n = (uint32_t)n;
+	in.fresh = !st0 || !st0->s_l_set;
+	in.ssrc_any = !st0;
+	in.ssrc = st0 ? st0->ssrc : 0;
+	in.roc = st0 ? st0->roc : 0;
+	in.s_l = st0 ? st0->s_l : 0;
+	in.lix = st0 ? st0->replay_rtp.lix : 0;
+	in.bitmap = st0 ? st0->replay_rtp.bitmap : 0;
+	in.tag = T;
+	in.maxlen = SGPU_CACHED_MAX(c0->mode);
+	in.hmac = !gcm;
+	in.lookback = RX_LOOKBACK;
+	in.zeroed = 1;
+	{
+		/* one launch: parse + end copy + zeroed plan out + comp map */
+		struct sgpu_prologue pro = {
+			es_d, (uint32_t *)ro_d, NULL, (uint32_t)(sizeof(*ro) / 4),
+			0, (uint32_t *)w->cm.d, c0->dev, NULL, NULL, 0, 0, 0, 0,
+			NULL, 0};
+		err = sgpu_parse_prologue(d->arena, d->arena_size, d->pos,
+					  d->end, hd_d, NULL, (uint32_t)n, 0,
+					  &pro, stream);
+	}
+	if (!err)
+		err = sgpu_plan_rx(&in, hd_d, d->pos, es_d, d->cap,
+				   d->arena_size, desc_d, w->mscr.d, scr, ro_d,
+				   stream);
+	if (!err) {
+		/* the general kernels (EALREADY packets: MAC only): AES-CM
+		 * picks the header class from skip[], GCM has one */
+		struct sgpu_compact C = {
+			d->pos, es_d, hd_d, desc_d, NULL,
+			(const uint32_t *)w->cm.d, NULL, 0, (uint32_t)n, vd_d,
+			save_d, &ro_d->nfail, 0, 1,
+			gcm ? &ro_d->fail : ro_d->skip, 0, NULL, NULL};
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, gcm ? 0 : -1, 0, stream);
+	}
+	if (!err)
+		err = sgpu_plan_rx_commit(ro_d, hd_d, w->mscr.d, es_d, d->pos,
+					  d->end, d->err, (uint32_t)n, T, stream);
+	if (!err)
+		err = sgpu_memcpy_d2h(ro, ro_d, sizeof(*ro), stream);
+	if (!err && hpos) {
+		err = sgpu_memcpy_d2h(w->ms.h, d->pos, n * 4, stream);
+		if (!err)
+			err = sgpu_memcpy_d2h(w->ms.h + n * 4, d->end, n * 4,
+					      stream);
+		if (!err)
+			err = sgpu_memcpy_d2h(w->ms.h + n * 8, d->err, n * 4,
+					      stream);
+	}
+	if (!err)
+		err = sgpu_stream_sync(stream);
+	if (err)
+		return err;
+	if (ro->fail) {
+		if (g_env.times)
+			fprintf(stderr, "re_srtp rx plan n=%zu: not settled "
+				"(SPF %#x)\n", n, ro->fail);
+		return -1;
+	}
+	if (ro->nfail) {
+		/* a forged packet: undo on the device (the results were not
+		 * written), fold on the host engine */
+		count(&g_cnt_misses, ro->nfail);
+		count(&g_cnt_folds, 1);
+		/* AES-CM: one guarded launch per header class, GCM: one */
+		for (q = 0; q < (gcm ? 1 : 4) && !err; q++) {
+			struct sgpu_compact C = {
+				d->pos, es_d, hd_d, desc_d, NULL,
+				(const uint32_t *)w->cm.d, NULL, 0, (uint32_t)n,
+				vd_d, save_d, &ro_d->nfail, 1, 1,
+				gcm ? &ro_d->fail : &ro_d->skip[q], 0, NULL, NULL};
+			err = sgpu_run_compact(d->arena, d->arena_size, &C,
+					       c0->mode, (int)c0->nr, q, 0, stream);
+		}
+		if (!err)
+			err = sgpu_stream_sync(stream);
+		return err ? err : -1;
+	}
+	if (!s->nstreams) {
+		memset(&s->streams[0], 0, sizeof(s->streams[0]));
+		s->streams[0].ssrc = ro->ssrc0;
+		s->nstreams = 1;
+	}
+	st = &s->streams[0];
+	st->s_l_set = 1;
+	st->roc = ro->roc;
+	st->s_l = (uint16_t)ro->s_l;
+	st->replay_rtp.lix = ro->lix;
+	st->replay_rtp.bitmap = ro->bitmap;
+	if (hpos) {
+		memcpy(hpos, w->ms.h, n * 4);
+		memcpy(hend, w->ms.h + n * 4, n * 4);
+		memcpy(herr, w->ms.h + n * 8, n * 4);
+	}
+	count(&g_cnt_rxplans, 1);
+	count(&g_cnt_rxlate, ro->nlate);
+	count(&g_cnt_rxdups, ro->ndup);
+	return 0;
 }
 
 /* ---- one session, several streams (plan_streams.hip) ------------------ */

@@ -1137,6 +1137,23 @@ static int run_fast(int op, struct srtp **sessv, size_t nsess,
 		}
 		if (capok)
 			memcpy(b->end, up_h + n, n * 4);
+		/* a rejected device plan, as the device-window calls count it */
+		if (po->fail)
+			count(&g_cnt_rejects, 1);
+		/* reordered or replayed arrivals: the receive planner, on the
+		 * staged windows (the results land in the session slot of
+		 * w->up, unused with one session, and are copied down) */
+		if (rx_eligible(op, ps, po->fail)) {
+			struct srtp_batch_dev rd = {
+				b->arena, b->arena_size, up_d, up_d + n, NULL,
+				(int32_t *)(up_d + 2 * n), NULL, n, stream};
+			const int r = dev_rxplanned(ps, &rd, b->pos, b->end,
+						    b->err);
+			if (r >= 0) {
+				free(fl);
+				return r;
+			}
+		}
 		/* not plannable: headers down for the host scan */
 		pst = stream;
 		err = sgpu_memcpy_d2h(w->hd.h, hd_d, n * sizeof(*hd_d), stream);

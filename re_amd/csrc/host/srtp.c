@@ -129,6 +129,11 @@ uint64_t g_cnt_mplans;   /* multi-session device plans accepted */
 uint64_t g_cnt_rplans;   /* SRTCP device plans (k_plan_rtcp) accepted */
 uint64_t g_cnt_lplans;   /* single-stream batches planned by the
 				   one-launch planner (k_lp_plan), accepted */
+uint64_t g_cnt_rxplans;  /* reordered / duplicated one-stream unprotect
+				   batches completed by the receive planner
+				   (plan_rx.hip) */
+uint64_t g_cnt_rxlate;   /* ... late packets it accepted */
+uint64_t g_cnt_rxdups;   /* ... EALREADY verdicts it gave */
 uint64_t g_cnt_lbtimeout; /* fused launches rejected by a look-back
 				   wait past its bound (SPF_SLOW) */
 /* a session's first batch (no stream yet) goes to the per-stream planner
@@ -184,6 +189,12 @@ uint64_t srtp_gpu_counter(const char *name)
 		return __atomic_load_n(&g_cnt_fused, __ATOMIC_RELAXED);
 	if (!strcmp(name, "lplans"))
 		return __atomic_load_n(&g_cnt_lplans, __ATOMIC_RELAXED);
+	if (!strcmp(name, "rxplans"))
+		return __atomic_load_n(&g_cnt_rxplans, __ATOMIC_RELAXED);
+	if (!strcmp(name, "rxlate"))
+		return __atomic_load_n(&g_cnt_rxlate, __ATOMIC_RELAXED);
+	if (!strcmp(name, "rxdups"))
+		return __atomic_load_n(&g_cnt_rxdups, __ATOMIC_RELAXED);
 	if (!strcmp(name, "dplans"))
 		return __atomic_load_n(&g_cnt_dplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "mplans"))
@@ -283,6 +294,8 @@ int srtp_gpu_tune(const char *name, long value)
 		g_env.nofuse = value > 0;
 	else if (!strcmp(name, "smallsync"))
 		g_env.smallsync = value > 0;
+	else if (!strcmp(name, "norxplan"))
+		g_env.norxplan = value > 0;
 	else if (!strcmp(name, "rxseq"))
 		g_env.rxseq = value > 0;
 	else if (!strcmp(name, "freshmulti"))

@@ -121,6 +121,11 @@ struct srtp_env {
 				   (default 1000) */
 	int rxseq;              /* srtp_gpu_tune rxseq: srtp_rx_index* and
 				   srtp_rx_fold walk sequentially (A/B) */
+	int norxplan;           /* srtp_gpu_tune norxplan: a one-stream
+				   unprotect plan rejected for reordered or
+				   replayed packets goes straight to the host
+				   engine, not to the receive planner
+				   (plan_rx.hip) */
 	int smallsync;          /* srtp_gpu_tune smallsync: wait for a small
 				   launch by a stream synchronisation, not
 				   its completion word */
@@ -278,6 +283,7 @@ extern uint64_t g_cnt_misses, g_cnt_folds, g_cnt_rejects, g_cnt_devfolds;
 extern uint64_t g_cnt_splans, g_cnt_fused, g_cnt_gated;
 extern uint64_t g_cnt_dplans, g_cnt_mplans, g_cnt_rplans, g_cnt_lbtimeout;
 extern uint64_t g_cnt_lplans;
+extern uint64_t g_cnt_rxplans, g_cnt_rxlate, g_cnt_rxdups;
 extern int g_fresh_multi;       /* srtp.c: the last first batch of a session
 				   showed several SSRCs (see there) */
 extern __thread struct tk_owner *t_own; /* srtp.c: this thread's async
@@ -411,6 +417,9 @@ int dev_planned_issue(struct dcall *k);
 int dev_planned_finish(struct dcall *k);
 int dev_planned(int op, struct srtp *s, struct srtp_batch_dev *d,
 		       uint32_t *pfail);
+int rx_eligible(int op, const struct srtp *s, uint32_t pfail);
+int dev_rxplanned(struct srtp *s, struct srtp_batch_dev *d, uint32_t *hpos,
+		  uint32_t *hend, int32_t *herr);
 int dev_splanned_issue(struct dcall *k);
 int dev_splanned_finish(struct dcall *k);
 int dev_splanned(int op, struct srtp *s, struct srtp_batch_dev *d);

@@ -390,6 +390,66 @@ int   sgpu_plan_rtp(const struct sgpu_plan_in *in, const struct sgpu_hdr *hdr,
 		    struct sgpu_plan_out *out, void *stream);
 
 /*
+ * Exact device plan of a single-stream RTP UNPROTECT batch that arrives
+ * reordered, duplicated or with gaps (plan_rx.hip; the rule:
+ * hip/plan_rx_rule.h) -- what the planners above reject with SPF_ORDER /
+ * SPF_REPLAY.  hdr / pos / end / cap as for sgpu_plan_rtp (cap may be
+ * NULL); desc is written as the host's sequential scan writes it (accepted:
+ * SD_RUN | SD_CIPHER; EALREADY: SD_RUN, GCM SD_RUN | SD_CIPHER).
+ * out->fail != 0: not settled, nothing modified, plan on the host.
+ * out->skip[] / out->fail guard the crypto launches behind it, which count
+ * their tag misses in out->nfail; sgpu_plan_rx_commit behind those writes
+ * the caller's pos / end / err (0 or EALREADY) unless fail or nfail.
+ */
+struct sgpu_rxplan_in {
+	uint32_t n;
+	uint32_t fresh;         /* s_l not set yet (first RTP packet) */
+	uint32_t ssrc;          /* existing stream's SSRC */
+	uint32_t ssrc_any;      /* no stream yet: take packet 0's SSRC */
+	uint32_t roc;
+	uint32_t s_l;
+	uint64_t lix;           /* replay_rtp */
+	uint64_t bitmap;
+	uint32_t tag;           /* bytes the tag removes */
+	uint32_t maxlen;        /* packets of maxlen bytes or more: SPF_SIZE */
+	uint32_t hmac;          /* HMAC suite: EALREADY packets are not
+				   decrypted */
+	uint32_t lookback;      /* arrivals searched for a duplicate's
+				   original (RX_LOOKBACK) */
+	uint32_t zeroed;        /* out already zeroed */
+	uint32_t pad;
+};
+
+struct sgpu_rxplan_out {
+	uint32_t fail;          /* SPF_* */
+	uint32_t nfail;         /* the crypto launches' tag misses */
+	uint32_t roc;           /* stream state after the batch */
+	uint32_t s_l;
+	uint64_t lix;
+	uint64_t bitmap;
+	uint32_t nlate;         /* packets accepted below the window's top */
+	uint32_t ndup;          /* EALREADY verdicts */
+	uint32_t skip[4];       /* guard of the shift-class-s crypto launch */
+	uint32_t ssrc0;
+	uint32_t hl0;           /* header length of packet 0 */
+};
+
+/* device scratch (64-byte aligned): u[] | Mx[] | block aggregates |
+ * per-packet verdicts */
+size_t sgpu_plan_rx_scratch(uint32_t n);
+int   sgpu_plan_rx(const struct sgpu_rxplan_in *in, const struct sgpu_hdr *hdr,
+		   const uint32_t *pos, const uint32_t *end, const uint32_t *cap,
+		   uint64_t arena_size, uint64_t *desc, void *scratch,
+		   size_t scratch_bytes, struct sgpu_rxplan_out *out,
+		   void *stream);
+/* es: the ends before the call (what the plan and the crypto launches
+ * read); pos / end / err: the caller's arrays */
+int   sgpu_plan_rx_commit(const struct sgpu_rxplan_out *out,
+			  const struct sgpu_hdr *hdr, const void *scratch,
+			  const uint32_t *es, uint32_t *pos, uint32_t *end,
+			  int32_t *err, uint32_t n, uint32_t tag, void *stream);
+
+/*
  * Multi-session device planning (many sessions with at most one RTP
  * stream each, e.g. 64K sessions x 1 SSRC): packets are stably sorted by
  * session on the device, every session's run of packets gets the

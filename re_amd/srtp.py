@@ -114,7 +114,8 @@ EXPORTS = (
     "srtp_decrypt_batch_dev", "srtcp_encrypt_batch_dev",
     "srtcp_decrypt_batch_dev", "srtp_encrypt_batch_dev_async",
     "srtp_decrypt_batch_dev_async", "srtp_batch_wait", "srtp_stream_export",
-    "srtp_stream_import", "srtp_rx_index", "srtp_rx_fold", "srtp_alloc_many", "srtp_gpu_error",
+    "srtp_stream_import", "srtp_rx_index", "srtp_rx_fold", "srtp_rx_plan_host",
+    "srtp_alloc_many", "srtp_gpu_error",
     "srtp_gpu_prof", "srtp_gpu_prof_read", "srtp_gpu_prof_read_named",
     "srtp_gpu_tune", "srtp_gpu_counter",
     "rtcp_decode_batch_dev",
@@ -175,6 +176,10 @@ def load():
                                     vp, vp, sz, vp, vp]
     L.srtp_rx_fold.argtypes = [ctypes.POINTER(StreamState), ctypes.c_int, vp,
                                sz, vp, ctypes.POINTER(sz)]
+    L.srtp_rx_plan_host.argtypes = [ctypes.POINTER(StreamState), vp, sz,
+                                    ctypes.c_uint32, ctypes.c_uint32, vp, vp,
+                                    ctypes.POINTER(StreamState),
+                                    ctypes.POINTER(ctypes.c_uint32)]
     L.srtp_gpu_prof.argtypes = [ctypes.c_int]
     L.srtp_gpu_tune.argtypes = [ctypes.c_char_p, ctypes.c_long]
     L.srtp_gpu_counter.argtypes = [ctypes.c_char_p]
@@ -279,6 +284,25 @@ class Srtp:
 
     def import_(self, st):
         return lib().srtp_stream_import(self.ptr, ctypes.byref(st))
+
+
+def rx_plan_host(st0, seq, block=256, lookback=128):
+    """srtp_rx_plan_host: the receive planner's rule on the CPU.  seq:
+    sequence numbers in arrival order; st0: StreamState before the batch.
+    Returns (fail, ix uint64 array, err int32 array, StreamState after)."""
+    import numpy as np
+    seq = np.ascontiguousarray(seq, dtype=np.uint16)
+    n = len(seq)
+    ix = np.zeros(n, dtype=np.uint64)
+    err = np.zeros(n, dtype=np.int32)
+    st1 = StreamState()
+    fail = ctypes.c_uint32(0)
+    rc = lib().srtp_rx_plan_host(ctypes.byref(st0), seq.ctypes.data, n,
+                                 block, lookback, ix.ctypes.data,
+                                 err.ctypes.data, ctypes.byref(st1),
+                                 ctypes.byref(fail))
+    assert rc == 0, rc
+    return fail.value, ix, err, st1
 
 
 def alloc_many(n, suite, keys, flags=0):
