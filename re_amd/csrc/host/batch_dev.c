@@ -1,13 +1,17 @@
 /*
  * batch_dev.c -- fully device-resident batches (srtp_*_batch_dev):
  * packets, positions and stream state stay in HBM and the plan runs on the
- * device -- one stream planned inside the crypto launch (k_ctr_fused.h,
- * fz_issue / fz_finish), one stream by the planner kernels
- * (dev_planned), several streams of one session (plan_streams.hip), SRTCP
+ * device -- one stream planned inside the crypto launch or by the
+ * one-launch planner in front of it (k_ctr_fused.h, fz_issue / fz_finish),
+ * one stream by the separate planner kernels (dp_issue / dp_finish;
+ * dev_planned picks among the three), reordered arrivals (plan_rx.hip),
+ * several streams of one session (plan_streams.hip), SRTCP
  * (dev_planned_rtcp) and many sessions with resident state
  * (dev_mplanned).  Each call is a struct dcall between its launches
- * (*_issue) and its completion (*_finish), so the synchronous calls and the
- * asynchronous tickets (batch_async.c) share it.  Split out of srtp.c.
+ * (*_issue) and its completion (*_finish), so the synchronous calls
+ * (dev_call) and the asynchronous tickets (batch_async.c) share it.  Where a
+ * call's arrays lie in the workspace pools: struct ws_layout (srtp_int.h)
+ * and, for w->fz, struct fz_layout.  Split out of srtp.c.
  */
 #include <errno.h>
 #include <pthread.h>
@@ -27,96 +31,112 @@
 #include "pool.h"
 #include "srtp_int.h"
 
-/* ---- fully device-resident batches ------------------------------------ */
+/* ---- what the planners below share ------------------------------------- */
 
-
-
-/* single-stream RTP batch planned and processed on the device: the
- * launches (no host synchronisation) */
-static int fz_issue(struct dcall *k, int sync);
-static int fz_finish(struct dcall *k, int sync);
-
-static int lp_issue(struct dcall *k, int sync);
-static int lp_finish(struct dcall *k, int sync);
-
-int dev_planned_issue(struct dcall *k)
+/* the crypto launch over a call's windows and its workspace layout: every
+ * packet, nothing guarded; the call sites name what differs */
+static struct sgpu_compact compact_of(const struct srtp_batch_dev *d,
+				      const struct ws_layout *L)
 {
-	if (!g_env.noplanfuse) {
-		if (k->sessv[0]->rtp.mode == SGPU_MODE_CTR && !g_env.lplan) {
-			k->fused = 1;
-			return fz_issue(k, 0);
-		}
-		k->fused = 2;
-		return lp_issue(k, 0);
-	}
+	return (struct sgpu_compact){
+		.pos = d->pos, .end = L->es, .hdr = L->hdr, .desc = L->desc,
+		.compmap = L->cm, .n = (uint32_t)d->n, .verdict = L->verdict,
+		.save = L->save, .nfail = L->nfail};
+}
+
+/* a rejected single-stream plan: -2 gated by the chained call before
+ * (nothing ran, nothing counted), else -1 */
+static int plan_rejected(uint32_t fail, unsigned ns0)
+{
+	if (fail & SPF_PRED)
+		return -2;
+	if ((fail & SPF_SSRC) && !ns0)
+		__atomic_store_n(&g_fresh_multi, 1, __ATOMIC_RELAXED);
+	count(&g_cnt_rejects, 1);
+	return -1;
+}
+
+/* stream state from a fold the device settled */
+static void fold_apply(struct srtp *s, const struct sgpu_fold_out *fo)
+{
+	struct srtp_stream *st = &s->streams[0];
+	st->s_l = (uint16_t)fo->s_l;
+	st->replay_rtp.lix = fo->lix;
+	st->replay_rtp.bitmap = fo->bitmap;
+	count(&g_cnt_devfolds, 1);
+}
+
+/* behind a call's undo launches (err: what queueing them returned): the
+ * original ends back, one synchronisation; -1 (nothing modified, the host
+ * takes over) or errno */
+static int undone(int err, const struct srtp_batch_dev *d, const uint32_t *es)
+{
+	if (!err)
+		err = sgpu_memcpy_d2d(d->end, es, d->n * 4, d->stream);
+	if (!err)
+		err = sgpu_stream_sync(d->stream);
+	return err ? err : -1;
+}
+
+/* ---- one stream, the separate planner (srtp_gpu_tune noplanfuse) ------ */
+
+/* k_parse, k_plan_*, the compact crypto launch, the verdict fold and the
+ * results: the launches (no host synchronisation) */
+static int dp_issue(struct dcall *k)
+{
 	const int prot = k->op == OP_RTP_ENC;
 	struct srtp *s = k->sessv[0];
 	struct srtp_batch_dev *d = &k->d;
 	struct ws *w = k->w;
 	const struct comp *c0 = &s->rtp;
+	const int gcm = c0->mode == SGPU_MODE_GCM;
 	const size_t n = d->n;
-	const uint32_t T = c0->mode == SGPU_MODE_GCM ? 16u : c0->tag_len;
-	const uint32_t need = prot ? (c0->mode == SGPU_MODE_GCM ? 16u :
-			      (T > 4 ? T : 4u)) : 0u;
+	const uint32_t T = gcm ? 16u : c0->tag_len;
+	const uint32_t need = prot ? (gcm ? 16u : (T > 4 ? T : 4u)) : 0u;
+	/* pl: plan out | plan scratch | fold out | fold scratch */
+	const size_t foff = (sizeof(struct sgpu_plan_out) + (n / 256 + 8) * 4 +
+			     63) & ~63ul;
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 12,
+		.vs = n * 9 + 72, .cm = 4,
+		.pl = foff + 64 + (n / 256 + 4) * 20, .es = n * 4};
+	struct ws_layout L;
 	struct sgpu_plan_out *po, *po_d;
 	struct sgpu_fold_out *fo_d;
-	struct sgpu_hdr *hd_d;
-	uint64_t *desc_d;
-	uint32_t *scr, *es_d, *save_d, *nfail_d, *flist_d;
-	uint32_t cm = c0->dev;
-	uint8_t *vd_d;
+	uint32_t *scr, *fscr;
 	void *stream = d->stream;       /* NULL: the default (null) stream */
-	size_t foff;
 	int err;
 
-	err = pool_reserve(w, &w->hd, n * sizeof(struct sgpu_hdr));
-	if (!err)
-		err = pool_reserve(w, &w->dsc, n * 12);
-	if (!err)
-		err = pool_reserve(w, &w->vs, n * 9 + 72);
-	if (!err)
-		err = pool_reserve(w, &w->cm, 4);
-	/* pl: plan out | plan scratch | fold out | fold scratch */
-	foff = (sizeof(struct sgpu_plan_out) + (n / 256 + 8) * 4 + 63) & ~63ul;
 	k->foff = foff;
-	if (!err)
-		err = pool_reserve(w, &w->pl, foff + 64 + (n / 256 + 4) * 20);
-	if (!err)
-		err = pool_reserve(w, &w->es, n * 4);
+	err = ws_layout_reserve(w, n, &z, &L);
 	if (err)
 		return err;
-	hd_d = (struct sgpu_hdr *)w->hd.d;
-	desc_d = (uint64_t *)w->dsc.d;
-	nfail_d = (uint32_t *)w->vs.d;
-	save_d = (uint32_t *)(w->vs.d + 64);
-	vd_d = w->vs.d + 64 + n * 4;
-	flist_d = (uint32_t *)(w->vs.d + ((64 + n * 5 + 3) & ~(size_t)3));
 	po = (struct sgpu_plan_out *)w->pl.h;
 	po_d = (struct sgpu_plan_out *)w->pl.d;
 	scr = (uint32_t *)(w->pl.d + sizeof(*po));
-	es_d = (uint32_t *)w->es.d;
+	fo_d = (struct sgpu_fold_out *)(w->pl.d + foff);
+	fscr = (uint32_t *)(w->pl.d + foff + 64);
 
 	plan_in(&k->in, s, (uint32_t)n, prot, T, need);
 	{
 		/* one launch: parse + end copy + zeroed counters + comp map */
 		struct sgpu_prologue pro = {
-			es_d, nfail_d, (uint32_t *)po_d, 1,
-			(uint32_t)(sizeof(*po) / 4), (uint32_t *)w->cm.d, cm, NULL, NULL,
-			0, 0, 0, 0, NULL, 0};
+			.end_copy = L.es, .z0 = L.nfail, .z1 = (uint32_t *)po_d,
+			.nz0 = 1, .nz1 = (uint32_t)(sizeof(*po) / 4),
+			.cm_out = L.cm, .cm = c0->dev};
 		k->in.zeroed = 1;
 		err = sgpu_parse_prologue(d->arena, d->arena_size, d->pos,
-					  d->end, hd_d, NULL, (uint32_t)n, 0,
+					  d->end, L.hdr, NULL, (uint32_t)n, 0,
 					  &pro, stream);
 	}
 	k->in.pred = k->pred;   /* the gate check rides in k_plan_count */
 	if (!err)
-		err = sgpu_plan_rtp(&k->in, hd_d, d->pos, es_d, d->cap,
-				    d->arena_size, desc_d, scr, po_d, stream);
+		err = sgpu_plan_rtp(&k->in, L.hdr, d->pos, L.es, d->cap,
+				    d->arena_size, L.desc, scr, po_d, stream);
 	if (!err) {
-		struct sgpu_compact C = {
-			d->pos, es_d, hd_d, desc_d, NULL,
-			(const uint32_t *)w->cm.d, NULL, 0, (uint32_t)n, vd_d,
-			save_d, nfail_d, 0, 1, NULL, 0, flist_d, NULL};
+		struct sgpu_compact C = compact_of(d, &L);
+		C.uniform = 1;
+		C.flist = L.flist;
 		err = run_classes(d->arena, d->arena_size, C, c0,
 				  po_d, prot, stream);
 	}
@@ -124,26 +144,21 @@ int dev_planned_issue(struct dcall *k)
 	 * do without a miss), so a forged packet neither gates the next
 	 * chained call nor waits for the host (sgpu_fold_rtp) */
 	k->devfold = !prot && !g_env.nodevfold;
-	fo_d = (struct sgpu_fold_out *)(w->pl.d + foff);
 	if (!err && k->devfold)
-		err = sgpu_fold_rtp(1, nfail_d, &k->in, hd_d, desc_d, vd_d, es_d,
-				    d->pos, d->end, d->err,
-				    c0->mode == SGPU_MODE_GCM,
-				    (uint32_t *)(w->pl.d + foff + 64), fo_d,
+		err = sgpu_fold_rtp(1, L.nfail, &k->in, L.hdr, L.desc, L.verdict,
+				    L.es, d->pos, d->end, d->err, gcm, fscr, fo_d,
 				    stream);
 	/* results, gate word and the miss count next to the plan: one
 	 * launch, one copy into pinned memory */
 	if (!err)
-		err = sgpu_plan_finish(&po_d->fail, es_d, d->end, d->err,
+		err = sgpu_plan_finish(&po_d->fail, L.es, d->end, d->err,
 				       (uint32_t)n,
-				       prot ? (int32_t)T : -(int32_t)T, nfail_d,
+				       prot ? (int32_t)T : -(int32_t)T, L.nfail,
 				       k->gate, &po_d->nfail,
 				       k->devfold ? &fo_d->fail : NULL, stream);
 	if (!err && k->devfold)
-		err = sgpu_fold_rtp(2, nfail_d, &k->in, hd_d, desc_d, vd_d, es_d,
-				    d->pos, d->end, d->err,
-				    c0->mode == SGPU_MODE_GCM,
-				    (uint32_t *)(w->pl.d + foff + 64), fo_d,
+		err = sgpu_fold_rtp(2, L.nfail, &k->in, L.hdr, L.desc, L.verdict,
+				    L.es, d->pos, d->end, d->err, gcm, fscr, fo_d,
 				    stream);
 	/* plan out and fold out in one copy */
 	if (!err)
@@ -152,90 +167,56 @@ int dev_planned_issue(struct dcall *k)
 	return err;
 }
 
-/* ... after its launches completed: 0 / errno, -1 not plannable or a
- * forged packet the host must fold (nothing modified), -2 gated by the
- * chained call before (nothing modified) */
-int dev_planned_finish(struct dcall *k)
+/* ... after its launches completed (as dev_planned_finish) */
+static int dp_finish(struct dcall *k)
 {
-	if (k->fused == 1)
-		return fz_finish(k, 0);
-	if (k->fused == 2)
-		return lp_finish(k, 0);
 	const int prot = k->op == OP_RTP_ENC;
 	struct srtp *s = k->sessv[0];
 	struct srtp_batch_dev *d = &k->d;
 	struct ws *w = k->w;
-	const struct comp *c0 = &s->rtp;
 	const size_t n = d->n;
 	const unsigned ns0 = s->nstreams;
-	const size_t foff = k->foff;
-	struct sgpu_plan_out *po = (struct sgpu_plan_out *)w->pl.h;
-	struct sgpu_plan_out *po_d = (struct sgpu_plan_out *)w->pl.d;
-	struct sgpu_hdr *hd_d = (struct sgpu_hdr *)w->hd.d;
-	uint64_t *desc_d = (uint64_t *)w->dsc.d;
-	uint32_t *nfail_d = (uint32_t *)w->vs.d;
-	uint32_t *save_d = (uint32_t *)(w->vs.d + 64);
-	uint8_t *vd_d = w->vs.d + 64 + n * 4;
-	uint32_t *es_d = (uint32_t *)w->es.d;
-	void *stream = d->stream;
+	const struct sgpu_plan_out *po = (const struct sgpu_plan_out *)w->pl.h;
+	const struct sgpu_fold_out *fo =
+		(const struct sgpu_fold_out *)(w->pl.h + k->foff);
+	const uint32_t nfail = po->nfail;
+	struct ws_layout L;
+	struct sgpu_compact C;
 	struct srtp_stream old;
-	uint32_t nfail;
-	int err = 0;
+	int r;
 
-	nfail = po->nfail;
 	k->pfail = po->fail;
-	if (po->fail) {
-		if (po->fail & SPF_PRED)
-			return -2;
-		if ((po->fail & SPF_SSRC) && !ns0)
-			__atomic_store_n(&g_fresh_multi, 1, __ATOMIC_RELAXED);
-		count(&g_cnt_rejects, 1);
-		return -1;
-	}
+	if (po->fail)
+		return plan_rejected(po->fail, ns0);
 	count(&g_cnt_dplans, 1);
 	if (nfail)
 		count(&g_cnt_misses, nfail);
 	plan_apply(s, po, prot, n, &old);
 	if (!nfail)
 		return 0;
-	/* a forged packet: fold the verdicts on the device.  The kernels
-	 * already left each forged packet as srtp_decrypt does (HMAC: the
-	 * ciphertext restored, the ROC over the tag; GCM: decrypted in
+	/* a forged packet: the verdicts were folded on the device behind the
+	 * kernels (dp_issue), the outcome came back with the plan.  The
+	 * kernels already left each forged packet as srtp_decrypt does (HMAC:
+	 * the ciphertext restored, the ROC over the tag; GCM: decrypted in
 	 * place); the fold checks that the speculated rollovers and indices
 	 * hold under the true s_l and writes the EAUTH results, s_l and the
 	 * replay window (sgpu_fold_rtp). */
-	if (!prot && k->devfold) {
-		/* folded on the device behind the kernels (dev_planned_issue);
-		 * its verdict came back with the plan */
-		const struct sgpu_fold_out *fo =
-			(const struct sgpu_fold_out *)(w->pl.h + foff);
-		if (!fo->fail) {
-			struct srtp_stream *st = &s->streams[0];
-			st->s_l = (uint16_t)fo->s_l;
-			st->replay_rtp.lix = fo->lix;
-			st->replay_rtp.bitmap = fo->bitmap;
-			count(&g_cnt_devfolds, 1);
-			return 0;
-		}
+	if (!prot && k->devfold && !fo->fail) {
+		fold_apply(s, fo);
+		return 0;
 	}
 	count(&g_cnt_folds, 1);
 	/* undo on the device, fold on the host engine */
-	{
-		struct sgpu_compact C = {
-			d->pos, es_d, hd_d, desc_d, NULL,
-			(const uint32_t *)w->cm.d, NULL, 0, (uint32_t)n, vd_d,
-			save_d, nfail_d, 1, 1, NULL, 0, NULL, NULL};
-		err = run_classes(d->arena, d->arena_size, C, c0,
-				  po_d, prot, stream);
-	}
-	if (!err)
-		err = sgpu_memcpy_d2d(d->end, es_d, n * 4, stream);
-	if (!err)
-		err = sgpu_stream_sync(stream);
-	if (err)
-		return err;
-	plan_unapply(s, ns0, &old);
-	return -1;
+	ws_layout_get(w, n, &L);
+	C = compact_of(d, &L);
+	C.undo = 1;
+	C.uniform = 1;
+	r = undone(run_classes(d->arena, d->arena_size, C, &s->rtp,
+			       (struct sgpu_plan_out *)w->pl.d, prot, d->stream),
+		   d, L.es);
+	if (r == -1)
+		plan_unapply(s, ns0, &old);
+	return r;
 }
 
 
@@ -244,16 +225,26 @@ int dev_planned_finish(struct dcall *k)
 #define FZ_HEAD 64u             /* ticket word, padded */
 
 /*
- * Single-stream AES-CM batch planned inside its crypto launch
- * (srtpgpu.h struct sgpu_fused): one launch parses, plans and encrypts /
- * decrypts.  Synchronous calls (dev_fused): with no forged packet nothing
- * else runs on the device; forged packets get their ciphertext back
- * (k_ctr_refix_list) and the device verdict fold (sgpu_fold_rtp) after the
- * synchronisation showed a miss.  Asynchronous calls (dev_planned_issue):
- * the refix and fold are queued behind the launch (each exits at once
- * without a miss) with the chained gate word, so no host round trip is
- * needed.  A rejected plan or a fold the device cannot settle: every
- * processed packet undone (sgpu_fused_undo), the ends restored, and -1
+ * Single-stream batch planned by the decoupled look-back plan of
+ * k_ctr_fused.h (srtpgpu.h struct sgpu_fused), k->fused:
+ *
+ * 1  AES-CM: inside its crypto launch -- one launch parses, plans and
+ *    encrypts / decrypts.  A rejected plan: every processed packet undone
+ *    (sgpu_fused_undo), the ends restored.
+ * 2  AES-GCM, and AES-CM with srtp_gpu_tune lplan: k_lp_plan plans the batch
+ *    in a launch of its own -- hdr, es, desc, the plan out with the class
+ *    guards skip[], the results of every packet planned -- and the lean
+ *    crypto kernel runs behind it, guarded by skip[] and out->fail (AES-CM:
+ *    k_ctr_fast_any) or by out->fail (GCM: k_gcmu), counting its tag misses
+ *    into out->nfail.  A rejected plan wrote no byte of the arena (the
+ *    crypto launch did nothing): only the ends are put back.
+ *
+ * With no forged packet nothing else runs on the device; forged packets
+ * get their ciphertext back (k_ctr_refix_list; GCM leaves them decrypted)
+ * and the device verdict fold (sgpu_fold_rtp) once the plan out showed a
+ * miss (fz_finish).  An asynchronous call sets its chained gate word with
+ * the plan out (plan_out_back), so no host round trip is needed.  A
+ * rejected plan or a fold the device cannot settle: undone, and -1
  * (k->pfail: the plan's SPF_* bits, 0 for a fold) -- the caller plans on
  * the host, as for the separate device planner.
  *
@@ -261,6 +252,61 @@ int dev_planned_finish(struct dcall *k)
  */
 #define FZ_FO_OFF ((sizeof(struct sgpu_plan_out) + 63u) & ~(size_t)63)
 #define FZ_SLOT (FZ_FO_OFF + 64u)
+#define FZ_BYTES(nblk) (FZ_HEAD + 2 * FZ_SLOT + (size_t)(nblk) * 8)
+
+/* the pieces of w->fz a call uses: its slot (par) and the other one */
+struct fz_layout {
+	uint32_t *ticket;
+	struct sgpu_plan_out *out;      /* this call's plan out ... */
+	struct sgpu_fold_out *fo;       /* ... and fold out */
+	struct sgpu_plan_out *out_next; /* the next call's: zeroed by this */
+	unsigned long long *agg;        /* look-back words */
+	struct sgpu_plan_out *out_h;    /* pinned mirrors of out and fo */
+	struct sgpu_fold_out *fo_h;
+};
+
+static struct fz_layout fz_layout_get(const struct ws *w, uint32_t par)
+{
+	const size_t off = FZ_HEAD + (size_t)par * FZ_SLOT;
+	const size_t next = FZ_HEAD + (size_t)(par ^ 1) * FZ_SLOT;
+	return (struct fz_layout){
+		.ticket = (uint32_t *)w->fz.d,
+		.out = (struct sgpu_plan_out *)(w->fz.d + off),
+		.fo = (struct sgpu_fold_out *)(w->fz.d + off + FZ_FO_OFF),
+		.out_next = (struct sgpu_plan_out *)(w->fz.d + next),
+		.agg = (unsigned long long *)(w->fz.d + FZ_HEAD + 2 * FZ_SLOT),
+		.out_h = (struct sgpu_plan_out *)(w->fz.h + off),
+		.fo_h = (struct sgpu_fold_out *)(w->fz.h + off + FZ_FO_OFF)};
+}
+
+/* the fused / one-launch planners' workspace state (w->fz for nblk
+ * workgroups), zeroed on a new pool, an epoch wrap or srtp_gpu_tune fzepoch
+ * (a test hook, one-shot for whichever thread's launch comes next: the
+ * look-back words are zeroed with it, so words of an epoch used since the
+ * last zeroing can never match) */
+static int fz_prepare(struct ws *w, uint32_t nblk, void *stream)
+{
+	int err = pool_reserve(w, &w->fz, FZ_BYTES(nblk));
+	const long e = __atomic_exchange_n(&g_env.fzepoch, 0,
+					   __ATOMIC_RELAXED);
+	if (err)
+		return err;
+	if (e > 0 && e <= 0xffff)
+		w->fz_d = NULL;
+	if (w->fz_d != w->fz.d || w->fz_epoch == 0 ||
+	    w->fz_epoch > 0xffffu) {
+		err = sgpu_memset(w->fz.d, 0, w->fz.cap, stream);
+		if (err)
+			return err;
+		w->fz_d = w->fz.d;
+		w->fz_epoch = 1;
+		w->fz_tbase = 0;
+		w->fz_par = 0;
+	}
+	if (e > 0 && e <= 0xffff)
+		w->fz_epoch = (uint32_t)e;
+	return 0;
+}
 
 /* the workspace's pinned completion word for synchronous single-stream
  * calls (srtp_gpu_tune syncspin), once */
@@ -306,9 +352,10 @@ static int sync_wait(struct dcall *k, void *stream)
  * for, as for a synchronous call, and a chained call queued behind one
  * with misses is gated and re-run; the zero-miss fold launches cost every
  * call ~25 us, a miss costs the call behind it a host round trip) */
-static int plan_out_back(struct dcall *k, int sync, struct sgpu_plan_out *out,
+static int plan_out_back(struct dcall *k, struct sgpu_plan_out *out,
 			 void *host, void *stream)
 {
+	const int sync = k->sync;
 	int err = 0;
 	k->devfold = 0;
 	if (!g_env.nopost) {
@@ -332,67 +379,37 @@ static int plan_out_back(struct dcall *k, int sync, struct sgpu_plan_out *out,
 	return err;
 }
 
-static int fz_issue(struct dcall *k, int sync)
+/* the launches (no host synchronisation) */
+static int fz_issue(struct dcall *k)
 {
 	const int prot = k->op == OP_RTP_ENC;
 	struct srtp *s = k->sessv[0];
 	struct srtp_batch_dev *d = &k->d;
 	const struct comp *c0 = &s->rtp;
+	const int gcm = c0->mode == SGPU_MODE_GCM;      /* k->fused == 2 only */
 	const size_t n = d->n;
-	const uint32_t T = c0->tag_len;
-	const uint32_t need = prot ? (T > 4 ? T : 4u) : 0u;
+	const uint32_t T = gcm ? 16u : c0->tag_len;
+	const uint32_t need = prot ? (gcm ? 16u : (T > 4 ? T : 4u)) : 0u;
 	const uint32_t B = sgpu_fused_block();
 	const uint32_t nblk = (uint32_t)((n + B - 1) / B);
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
+		.vs = n * 9 + 72, .cm = 4, .pl = 64 + (n / 256 + 4) * 20,
+		.es = n * 4, .es_first = 1};
 	struct ws *w = k->w;
 	struct sgpu_fused *F = &k->fz;
+	struct ws_layout L;
+	struct fz_layout Z;
 	void *stream = d->stream;
-	uint8_t *fz;
-	size_t poff;
 	int err;
 
-	err = pool_reserve(w, &w->hd, n * sizeof(struct sgpu_hdr));
+	err = ws_layout_reserve(w, n, &z, &L);
 	if (!err)
-		err = pool_reserve(w, &w->dsc, n * 8);
-	if (!err)
-		err = pool_reserve(w, &w->vs, n * 9 + 72);
-	if (!err)
-		err = pool_reserve(w, &w->cm, 4);
-	if (!err)
-		err = pool_reserve(w, &w->es, n * 4);
-	if (!err)
-		err = pool_reserve(w, &w->pl, 64 + (n / 256 + 4) * 20);
-	if (!err)
-		err = pool_reserve(w, &w->fz, FZ_HEAD + 2 * FZ_SLOT +
-				   (size_t)nblk * 8);
+		err = fz_prepare(w, nblk, stream);
 	if (err)
 		return err;
-	fz = w->fz.d;
-	{
-		/* srtp_gpu_tune fzepoch (a test hook, one-shot for whichever
-		 * thread's fused launch comes next): the look-back words are
-		 * zeroed with it, so words of an epoch used since the last
-		 * zeroing can never match */
-		const long e = __atomic_exchange_n(&g_env.fzepoch, 0,
-						   __ATOMIC_RELAXED);
-		if (e > 0 && e <= 0xffff)
-			w->fz_d = NULL;
-		if (w->fz_d != fz || w->fz_epoch == 0 ||
-		    w->fz_epoch > 0xffffu) {
-			/* a new pool (or the look-back epoch wrapped):
-			 * counters, plan outs and look-back words from zero */
-			err = sgpu_memset(fz, 0, w->fz.cap, stream);
-			if (err)
-				return err;
-			w->fz_d = fz;
-			w->fz_epoch = 1;
-			w->fz_tbase = 0;
-			w->fz_par = 0;
-		}
-		if (e > 0 && e <= 0xffff)
-			w->fz_epoch = (uint32_t)e;
-	}
-	poff = FZ_HEAD + (size_t)w->fz_par * FZ_SLOT;
-	k->foff = poff;
+	k->foff = w->fz_par;
+	Z = fz_layout_get(w, w->fz_par);
 
 	memset(F, 0, sizeof(*F));
 	plan_in(&F->in, s, (uint32_t)n, prot, T, need);
@@ -402,26 +419,26 @@ static int fz_issue(struct dcall *k, int sync)
 	F->end = d->end;
 	F->cap = d->cap;
 	F->err = d->err;
-	F->es = (uint32_t *)w->es.d;
-	F->hdr = (struct sgpu_hdr *)w->hd.d;
-	F->desc = (uint64_t *)w->dsc.d;
+	F->es = L.es;
+	F->hdr = L.hdr;
+	F->desc = L.desc;
 	if (!prot) {
-		F->save = (uint32_t *)(w->vs.d + 64);
-		F->verdict = w->vs.d + 64 + n * 4;
-		F->flist = (uint32_t *)(w->vs.d +
-					((64 + n * 5 + 3) & ~(size_t)3));
+		F->save = L.save;
+		F->verdict = L.verdict;
+		F->flist = gcm ? NULL : L.flist;
 	}
-	F->out = (struct sgpu_plan_out *)(fz + poff);
-	F->out_next = (struct sgpu_plan_out *)(fz + FZ_HEAD +
-					       (size_t)(w->fz_par ^ 1) * FZ_SLOT);
-	F->cm_out = (uint32_t *)w->cm.d;
-	F->agg = (unsigned long long *)(fz + FZ_HEAD + 2 * FZ_SLOT);
-	F->ticket = (uint32_t *)fz;
+	F->out = Z.out;
+	F->out_next = Z.out_next;
+	F->cm_out = L.cm;
+	F->agg = Z.agg;
+	F->ticket = Z.ticket;
 	F->tbase = w->fz_tbase;
 	F->epoch = w->fz_epoch;
 	F->comp = c0->dev;
 	F->delta = prot ? (int32_t)T : -(int32_t)T;
-	err = sgpu_run_fused(d->arena, d->arena_size, F, (int)c0->nr, stream);
+	err = k->fused == 1 ? sgpu_run_fused(d->arena, d->arena_size, F,
+					     (int)c0->nr, stream)
+			    : sgpu_run_fzplan(d->arena, d->arena_size, F, stream);
 	if (err) {
 		w->fz_d = NULL;         /* counters unknown: from zero next time */
 		return err;
@@ -429,80 +446,92 @@ static int fz_issue(struct dcall *k, int sync)
 	w->fz_tbase += F->ntickets;
 	w->fz_epoch++;
 	w->fz_par ^= 1;
-	return plan_out_back(k, sync, F->out, w->fz.h + poff, stream);
+	if (k->fused == 2) {
+		/* the crypto launch behind the plan's guards */
+		struct sgpu_compact C = {
+			.pos = d->pos, .end = F->es, .hdr = F->hdr,
+			.desc = F->desc, .compmap = F->cm_out, .n = (uint32_t)n,
+			.verdict = F->verdict, .save = F->save,
+			.nfail = &F->out->nfail, .uniform = gcm ? 1 : 2,
+			.guard = gcm ? &F->out->fail : F->out->skip,
+			.flist = F->flist, .gfail = gcm ? NULL : &F->out->fail};
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, gcm ? 0 : -1, prot, stream);
+		if (err)
+			return err;
+	}
+	return plan_out_back(k, F->out, Z.out_h, stream);
 }
 
-/* ... after its launches completed: 0 / errno, -1 not plannable or a
- * forged packet the host must fold (nothing modified), -2 gated by the
- * chained call before (nothing modified) */
-static int fz_finish(struct dcall *k, int sync)
+/* ... after its launches completed (as dev_planned_finish) */
+static int fz_finish(struct dcall *k)
 {
 	const int prot = k->op == OP_RTP_ENC;
+	const int lean = k->fused == 2;
 	struct srtp *s = k->sessv[0];
 	struct srtp_batch_dev *d = &k->d;
 	const struct comp *c0 = &s->rtp;
+	const int gcm = c0->mode == SGPU_MODE_GCM;      /* lean only */
 	const size_t n = d->n;
 	const unsigned ns0 = s->nstreams;
 	struct ws *w = k->w;
 	struct sgpu_fused *F = &k->fz;
-	const size_t poff = k->foff;
-	const struct sgpu_plan_out *po =
-		(const struct sgpu_plan_out *)(w->fz.h + poff);
-	const struct sgpu_fold_out *fo =
-		(const struct sgpu_fold_out *)(w->fz.h + poff + FZ_FO_OFF);
+	const struct fz_layout Z = fz_layout_get(w, (uint32_t)k->foff);
+	const struct sgpu_plan_out *po = Z.out_h;
 	void *stream = d->stream;
 	struct srtp_stream old;
-	int err;
+	int err = 0;
 
 	k->pfail = po->fail;
 	if (po->fail) {
 		/* no work that counts: nothing (gated) or undone */
-		sgpu_prof_void(F->prof_id);
-		if (po->fail & SPF_PRED)
+		if (!lean)
+			sgpu_prof_void(F->prof_id);
+		if (plan_rejected(po->fail, ns0) == -2)
 			return -2;      /* every workgroup did nothing */
 		if (po->fail & (SPF_BAD | SPF_SLOW))
 			w->fz_d = NULL; /* ticket / look-back state from zero */
 		if (po->fail & SPF_SLOW)
 			count(&g_cnt_lbtimeout, 1);
-		if ((po->fail & SPF_SSRC) && !ns0)
-			__atomic_store_n(&g_fresh_multi, 1, __ATOMIC_RELAXED);
-		count(&g_cnt_rejects, 1);
-		goto undo;
+		if (!lean)
+			goto undo;
+		if (g_env.times)
+			fprintf(stderr, "re_srtp plan n=%zu %s: rejected "
+				"(SPF %#x)\n", n, prot ? "protect" : "unprotect",
+				po->fail);
+		/* the crypto launch did nothing: only the ends the plan wrote
+		 * go back */
+		return undone(0, d, F->es);
 	}
 	plan_apply(s, po, prot, n, &old);
-	count(&g_cnt_fused, 1);
+	count(lean ? &g_cnt_lplans : &g_cnt_fused, 1);
 	if (!po->nfail)
 		return 0;
 	count(&g_cnt_misses, po->nfail);
-	(void)sync;
 	if (!g_env.nodevfold) {
-		/* forged packets: ciphertext back, verdicts folded on the
-		 * device; its outcome comes back in one copy */
-		struct sgpu_fold_out *fo_d =
-			(struct sgpu_fold_out *)(w->fz.d + poff + FZ_FO_OFF);
-		err = sgpu_fused_refix(d->arena, d->arena_size, F,
-				       (int)c0->nr, stream);
+		/* forged packets: ciphertext back (GCM leaves them decrypted),
+		 * verdicts folded on the device; its outcome comes back in one
+		 * copy */
+		if (!gcm)
+			err = sgpu_fused_refix(d->arena, d->arena_size, F,
+					       (int)c0->nr, stream);
 		if (!err)
 			err = sgpu_fold_rtp(0, &F->out->nfail, &F->in, F->hdr,
 					    F->desc, F->verdict, F->es, d->pos,
-					    d->end, d->err, 0,
-					    (uint32_t *)(w->pl.d + 64), fo_d,
+					    d->end, d->err, gcm,
+					    (uint32_t *)(w->pl.d + 64), Z.fo,
 					    stream);
 		if (!err)
-			err = sgpu_memcpy_d2h(w->fz.h + poff + FZ_FO_OFF, fo_d,
-					      sizeof(*fo), stream);
+			err = sgpu_memcpy_d2h(Z.fo_h, Z.fo, sizeof(*Z.fo),
+					      stream);
 		if (!err)
 			err = sgpu_stream_sync(stream);
 		if (err)
 			return err;
 		k->devfold = 1;
 	}
-	if (k->devfold && !fo->fail) {
-		struct srtp_stream *st = &s->streams[0];
-		st->s_l = (uint16_t)fo->s_l;
-		st->replay_rtp.lix = fo->lix;
-		st->replay_rtp.bitmap = fo->bitmap;
-		count(&g_cnt_devfolds, 1);
+	if (k->devfold && !Z.fo_h->fail) {
+		fold_apply(s, Z.fo_h);
 		return 0;
 	}
 	/* the fold cannot be settled on the device (or nodevfold): undo --
@@ -511,49 +540,85 @@ static int fz_finish(struct dcall *k, int sync)
 	count(&g_cnt_folds, 1);
 	plan_unapply(s, ns0, &old);
  undo:
-	if (po->hl0 != 0xffffffffu) {
+	if (gcm) {
+		struct sgpu_compact C = {
+			.pos = d->pos, .end = F->es, .hdr = F->hdr,
+			.desc = F->desc, .compmap = F->cm_out, .n = (uint32_t)n,
+			.verdict = F->verdict, .save = F->save,
+			.nfail = &F->out->nfail, .undo = 1, .uniform = 1};
+		err = run_classes(d->arena, d->arena_size, C, c0, F->out, prot,
+				  stream);
+	}
+	else if (lean || po->hl0 != 0xffffffffu) {
 		F->shift = (po->hl0 >> 2) & 3u;
 		err = sgpu_fused_undo(d->arena, d->arena_size, F, (int)c0->nr,
 				      prot, stream);
-		if (err)
-			return err;
 	}
-	err = sgpu_memcpy_d2d(d->end, F->es, n * 4, stream);
-	if (!err)
-		err = sgpu_stream_sync(stream);
-	return err ? err : -1;
+	return undone(err, d, F->es);
 }
 
-/* synchronous (dev_planned): -1 not plannable (nothing modified;
- * *pfail: why, 0 for a forged packet the host must fold), else 0 /
- * errno */
-static int dev_fused(int op, struct srtp *s, struct srtp_batch_dev *d,
-		     uint32_t *pfail)
+/* ---- one stream: which planner, and the synchronous calls ------------- */
+
+/* 1: the plan inside the crypto launch, 2: the one-launch planner in front
+ * of the lean kernels, 0: the separate planner (struct dcall fused) */
+static int planned_kind(const struct srtp *s)
+{
+	if (g_env.noplanfuse)
+		return 0;
+	return s->rtp.mode == SGPU_MODE_CTR && !g_env.lplan ? 1 : 2;
+}
+
+/* single-stream RTP batch planned and processed on the device: the
+ * launches (no host synchronisation) */
+int dev_planned_issue(struct dcall *k)
+{
+	k->fused = planned_kind(k->sessv[0]);
+	return k->fused ? fz_issue(k) : dp_issue(k);
+}
+
+/* ... after its launches completed: 0 / errno, -1 not plannable or a
+ * forged packet the host must fold (nothing modified), -2 gated by the
+ * chained call before (nothing modified) */
+int dev_planned_finish(struct dcall *k)
+{
+	return k->fused ? fz_finish(k) : dp_finish(k);
+}
+
+/* a synchronous device-planned call: issue, wait, finish (*pfail: a
+ * rejected plan's SPF_* bits).  timed: the call may be waited for by its
+ * post's completion word (sync_wait), and where its host time goes is
+ * counted (counters sync_ns_issue / _wait / _finish) */
+static inline int dev_call(int op, struct srtp **sessv, size_t nsess,
+			   struct srtp_batch_dev *d, int radix,
+			   int (*issue)(struct dcall *),
+			   int (*finish)(struct dcall *), int timed,
+			   uint32_t *pfail)
 {
 	struct dcall k;
+	uint64_t t0, t1, t2;
 	int err;
 	memset(&k, 0, sizeof(k));
 	k.op = op;
-	k.sessv = &s;
-	k.nsess = 1;
+	k.sessv = sessv;
+	k.nsess = nsess;
 	k.d = *d;
+	k.sync = 1;
+	k.radix = radix;
 	k.w = ws_get();
 	*pfail = 0;
 	if (!k.w)
 		return ENOMEM;
-	{
-		/* where a synchronous call's host time goes (counters
-		 * sync_ns_issue / _wait / _finish) */
-		const uint64_t t0 = mono_ns();
-		uint64_t t1, t2;
-		err = fz_issue(&k, 1);
-		t1 = mono_ns();
-		if (!err)
-			err = sync_wait(&k, d->stream);
-		t2 = mono_ns();
-		if (err)
-			return err;
-		err = fz_finish(&k, 1);
+	t0 = timed ? mono_ns() : 0;
+	err = issue(&k);
+	t1 = timed ? mono_ns() : 0;
+	if (!err)
+		err = timed ? sync_wait(&k, d->stream)
+			    : sgpu_stream_sync(d->stream);
+	t2 = timed ? mono_ns() : 0;
+	if (err)
+		return err;
+	err = finish(&k);
+	if (timed) {
 		count(&g_cnt_sync_calls, 1);
 		count(&g_ns_sync_issue, t1 - t0);
 		count(&g_ns_sync_wait, t2 - t1);
@@ -563,293 +628,13 @@ static int dev_fused(int op, struct srtp *s, struct srtp_batch_dev *d,
 	return err;
 }
 
-/* ---- one stream, the one-launch planner in front of the lean kernels -- */
-
-/*
- * k_lp_plan (k_ctr_fused.h) plans the batch in one launch -- the in-launch
- * plan of k_ctr_fused as a kernel of its own: hdr, es, desc, the plan out
- * with the class guards skip[], the results of every packet planned -- and
- * the lean crypto kernel runs behind it, guarded by skip[] and out->fail
- * (AES-CM: k_ctr_fast_any) or by out->fail (GCM: k_gcmu), counting its
- * tag misses into out->nfail.  A rejected plan wrote no byte of the arena
- * (the crypto launch did nothing): only the ends are put back.  Forged
- * packets: as dev_fused (the restore of their ciphertext and the verdict
- * fold after the synchronisation; queued behind for asynchronous calls).
- * Same workspace state as fz_issue (w->fz: tickets, epochs, plan outs).
- */
-/* the fused / one-launch planners' workspace state (w->fz: ticket |
- * (plan out, fold out) x 2 | look-back words for nblk workgroups), zeroed
- * on a new pool, an epoch wrap or the fzepoch hook */
-static int fz_prepare(struct ws *w, uint32_t nblk, void *stream)
-{
-	int err = pool_reserve(w, &w->fz, FZ_HEAD + 2 * FZ_SLOT +
-			       (size_t)nblk * 8);
-	const long e = __atomic_exchange_n(&g_env.fzepoch, 0,
-					   __ATOMIC_RELAXED);
-	if (err)
-		return err;
-	if (e > 0 && e <= 0xffff)
-		w->fz_d = NULL;
-	if (w->fz_d != w->fz.d || w->fz_epoch == 0 ||
-	    w->fz_epoch > 0xffffu) {
-		err = sgpu_memset(w->fz.d, 0, w->fz.cap, stream);
-		if (err)
-			return err;
-		w->fz_d = w->fz.d;
-		w->fz_epoch = 1;
-		w->fz_tbase = 0;
-		w->fz_par = 0;
-	}
-	if (e > 0 && e <= 0xffff)
-		w->fz_epoch = (uint32_t)e;
-	return 0;
-}
-
-static int lp_issue(struct dcall *k, int sync)
-{
-	const int prot = k->op == OP_RTP_ENC;
-	struct srtp *s = k->sessv[0];
-	struct srtp_batch_dev *d = &k->d;
-	const struct comp *c0 = &s->rtp;
-	const int gcm = c0->mode == SGPU_MODE_GCM;
-	const size_t n = d->n;
-	const uint32_t T = gcm ? 16u : c0->tag_len;
-	const uint32_t need = prot ? (gcm ? 16u : (T > 4 ? T : 4u)) : 0u;
-	const uint32_t B = sgpu_fused_block();
-	const uint32_t nblk = (uint32_t)((n + B - 1) / B);
-	struct ws *w = k->w;
-	struct sgpu_fused *F = &k->fz;
-	void *stream = d->stream;
-	uint8_t *fz;
-	size_t poff;
-	int err;
-
-	err = pool_reserve(w, &w->hd, n * sizeof(struct sgpu_hdr));
-	if (!err)
-		err = pool_reserve(w, &w->dsc, n * 8);
-	if (!err)
-		err = pool_reserve(w, &w->vs, n * 9 + 72);
-	if (!err)
-		err = pool_reserve(w, &w->cm, 4);
-	if (!err)
-		err = pool_reserve(w, &w->es, n * 4);
-	if (!err)
-		err = pool_reserve(w, &w->pl, 64 + (n / 256 + 4) * 20);
-	if (!err)
-		err = fz_prepare(w, nblk, stream);
-	if (err)
-		return err;
-	fz = w->fz.d;
-	poff = FZ_HEAD + (size_t)w->fz_par * FZ_SLOT;
-	k->foff = poff;
-
-	memset(F, 0, sizeof(*F));
-	plan_in(&F->in, s, (uint32_t)n, prot, T, need);
-	F->in.zeroed = 1;
-	F->in.pred = k->pred;
-	F->pos = d->pos;
-	F->end = d->end;
-	F->cap = d->cap;
-	F->err = d->err;
-	F->es = (uint32_t *)w->es.d;
-	F->hdr = (struct sgpu_hdr *)w->hd.d;
-	F->desc = (uint64_t *)w->dsc.d;
-	if (!prot) {
-		F->save = (uint32_t *)(w->vs.d + 64);
-		F->verdict = w->vs.d + 64 + n * 4;
-		F->flist = gcm ? NULL : (uint32_t *)(w->vs.d +
-				     ((64 + n * 5 + 3) & ~(size_t)3));
-	}
-	F->out = (struct sgpu_plan_out *)(fz + poff);
-	F->out_next = (struct sgpu_plan_out *)(fz + FZ_HEAD +
-					       (size_t)(w->fz_par ^ 1) * FZ_SLOT);
-	F->cm_out = (uint32_t *)w->cm.d;
-	F->agg = (unsigned long long *)(fz + FZ_HEAD + 2 * FZ_SLOT);
-	F->ticket = (uint32_t *)fz;
-	F->tbase = w->fz_tbase;
-	F->epoch = w->fz_epoch;
-	F->comp = c0->dev;
-	F->delta = prot ? (int32_t)T : -(int32_t)T;
-	err = sgpu_run_fzplan(d->arena, d->arena_size, F, stream);
-	if (err) {
-		w->fz_d = NULL;
-		return err;
-	}
-	w->fz_tbase += F->ntickets;
-	w->fz_epoch++;
-	w->fz_par ^= 1;
-	{
-		/* the crypto launch behind the plan's guards */
-		struct sgpu_compact C = {
-			d->pos, F->es, F->hdr, F->desc, NULL, F->cm_out, NULL, 0,
-			(uint32_t)n, F->verdict, F->save, &F->out->nfail, 0,
-			gcm ? 1 : 2, gcm ? &F->out->fail : F->out->skip, 0,
-			F->flist, gcm ? NULL : &F->out->fail};
-		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
-				       (int)c0->nr, gcm ? 0 : -1, prot, stream);
-		if (err)
-			return err;
-	}
-	return plan_out_back(k, sync, F->out, w->fz.h + poff, stream);
-}
-
-static int lp_finish(struct dcall *k, int sync)
-{
-	const int prot = k->op == OP_RTP_ENC;
-	struct srtp *s = k->sessv[0];
-	struct srtp_batch_dev *d = &k->d;
-	const struct comp *c0 = &s->rtp;
-	const int gcm = c0->mode == SGPU_MODE_GCM;
-	const size_t n = d->n;
-	const unsigned ns0 = s->nstreams;
-	struct ws *w = k->w;
-	struct sgpu_fused *F = &k->fz;
-	const size_t poff = k->foff;
-	const struct sgpu_plan_out *po =
-		(const struct sgpu_plan_out *)(w->fz.h + poff);
-	const struct sgpu_fold_out *fo =
-		(const struct sgpu_fold_out *)(w->fz.h + poff + FZ_FO_OFF);
-	void *stream = d->stream;
-	struct srtp_stream old;
-	int err;
-
-	k->pfail = po->fail;
-	if (po->fail) {
-		if (po->fail & SPF_PRED)
-			return -2;      /* every workgroup did nothing */
-		if (po->fail & (SPF_BAD | SPF_SLOW))
-			w->fz_d = NULL;
-		if (po->fail & SPF_SLOW)
-			count(&g_cnt_lbtimeout, 1);
-		if ((po->fail & SPF_SSRC) && !ns0)
-			__atomic_store_n(&g_fresh_multi, 1, __ATOMIC_RELAXED);
-		count(&g_cnt_rejects, 1);
-		if (g_env.times)
-			fprintf(stderr, "re_srtp plan n=%zu %s: rejected "
-				"(SPF %#x)\n", n, prot ? "protect" : "unprotect",
-				po->fail);
-		/* the crypto launch did nothing: only the ends the plan wrote
-		 * go back */
-		err = sgpu_memcpy_d2d(d->end, F->es, n * 4, stream);
-		if (!err)
-			err = sgpu_stream_sync(stream);
-		return err ? err : -1;
-	}
-	plan_apply(s, po, prot, n, &old);
-	count(&g_cnt_lplans, 1);
-	if (!po->nfail)
-		return 0;
-	count(&g_cnt_misses, po->nfail);
-	(void)sync;
-	if (!g_env.nodevfold) {
-		struct sgpu_fold_out *fo_d =
-			(struct sgpu_fold_out *)(w->fz.d + poff + FZ_FO_OFF);
-		err = 0;
-		if (!gcm)
-			err = sgpu_fused_refix(d->arena, d->arena_size, F,
-					       (int)c0->nr, stream);
-		if (!err)
-			err = sgpu_fold_rtp(0, &F->out->nfail, &F->in, F->hdr,
-					    F->desc, F->verdict, F->es, d->pos,
-					    d->end, d->err, gcm,
-					    (uint32_t *)(w->pl.d + 64), fo_d,
-					    stream);
-		if (!err)
-			err = sgpu_memcpy_d2h(w->fz.h + poff + FZ_FO_OFF, fo_d,
-					      sizeof(*fo), stream);
-		if (!err)
-			err = sgpu_stream_sync(stream);
-		if (err)
-			return err;
-		k->devfold = 1;
-	}
-	if (k->devfold && !fo->fail) {
-		struct srtp_stream *st = &s->streams[0];
-		st->s_l = (uint16_t)fo->s_l;
-		st->replay_rtp.lix = fo->lix;
-		st->replay_rtp.bitmap = fo->bitmap;
-		count(&g_cnt_devfolds, 1);
-		return 0;
-	}
-	/* the fold cannot be settled on the device (or nodevfold): every
-	 * processed packet back to its bytes, the host folds */
-	count(&g_cnt_folds, 1);
-	plan_unapply(s, ns0, &old);
-	if (gcm) {
-		struct sgpu_compact C = {
-			d->pos, F->es, F->hdr, F->desc, NULL, F->cm_out, NULL, 0,
-			(uint32_t)n, F->verdict, F->save, &F->out->nfail, 1, 1,
-			NULL, 0, NULL, NULL};
-		err = run_classes(d->arena, d->arena_size, C, c0, F->out, prot,
-				  stream);
-	}
-	else {
-		F->shift = (po->hl0 >> 2) & 3u;
-		err = sgpu_fused_undo(d->arena, d->arena_size, F, (int)c0->nr,
-				      prot, stream);
-	}
-	if (!err)
-		err = sgpu_memcpy_d2d(d->end, F->es, n * 4, stream);
-	if (!err)
-		err = sgpu_stream_sync(stream);
-	return err ? err : -1;
-}
-
-/* synchronous (dev_planned): -1 not plannable (nothing modified;
- * *pfail: why, 0 for a forged packet the host must fold), else 0 /
- * errno */
-static int dev_lplanned(int op, struct srtp *s, struct srtp_batch_dev *d,
-			uint32_t *pfail)
-{
-	struct dcall k;
-	int err;
-	memset(&k, 0, sizeof(k));
-	k.op = op;
-	k.sessv = &s;
-	k.nsess = 1;
-	k.d = *d;
-	k.w = ws_get();
-	*pfail = 0;
-	if (!k.w)
-		return ENOMEM;
-	err = lp_issue(&k, 1);
-	if (!err)
-		err = sgpu_stream_sync(d->stream);
-	if (err)
-		return err;
-	err = lp_finish(&k, 1);
-	*pfail = k.pfail;
-	return err;
-}
-
 /* synchronous: -1 not plannable (nothing modified; *pfail: why, 0 for a
  * forged packet the host must fold), else 0 / errno */
 int dev_planned(int op, struct srtp *s, struct srtp_batch_dev *d,
 		       uint32_t *pfail)
 {
-	struct dcall k;
-	int err;
-	if (!g_env.noplanfuse) {
-		if (s->rtp.mode == SGPU_MODE_CTR && !g_env.lplan)
-			return dev_fused(op, s, d, pfail);
-		return dev_lplanned(op, s, d, pfail);
-	}
-	memset(&k, 0, sizeof(k));
-	k.op = op;
-	k.sessv = &s;
-	k.nsess = 1;
-	k.d = *d;
-	k.w = ws_get();
-	if (!k.w)
-		return ENOMEM;
-	err = dev_planned_issue(&k);
-	if (!err)
-		err = sgpu_stream_sync(d->stream);
-	if (err)
-		return err;
-	err = dev_planned_finish(&k);
-	*pfail = k.pfail;
-	return err;
+	return dev_call(op, &s, 1, d, 0, dev_planned_issue, dev_planned_finish,
+			planned_kind(s) == 1, pfail);
 }
 
 /* ---- one stream, reordered / duplicated arrivals (plan_rx.hip) -------- */
@@ -972,13 +757,15 @@ int dev_rxplanned(struct srtp *s, struct srtp_batch_dev *d, uint32_t *hpos,
 	const uint32_t T = gcm ? 16u : c0->tag_len;
 	const size_t scr = sgpu_plan_rx_scratch((uint32_t)n);
 	const struct srtp_stream *st0 = s->nstreams ? &s->streams[0] : NULL;
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
+		.vs = n * 5 + 64, .cm = 4,
+		.pl = 64 + sizeof(struct sgpu_rxplan_out), .es = n * 4};
+	struct ws_layout L;
+	struct sgpu_compact C;
 	struct sgpu_rxplan_in in;
 	struct sgpu_rxplan_out *ro, *ro_d;
-	struct sgpu_hdr *hd_d;
 	struct srtp_stream *st;
-	uint64_t *desc_d;
-	uint32_t *es_d, *save_d;
-	uint8_t *vd_d;
 	void *stream = d->stream;
 	struct ws *w = ws_get();
 	int err, q;
@@ -988,30 +775,15 @@ int dev_rxplanned(struct srtp *s, struct srtp_batch_dev *d, uint32_t *hpos,
 	/* the rule computes in signed 64 bits (an imported window) */
 	if (st0 && (st0->replay_rtp.lix >> 62))
 		return -1;
-	err = pool_reserve(w, &w->hd, n * sizeof(struct sgpu_hdr));
-	if (!err)
-		err = pool_reserve(w, &w->dsc, n * 8);
-	if (!err)
-		err = pool_reserve(w, &w->vs, n * 5 + 64);
-	if (!err)
-		err = pool_reserve(w, &w->cm, 4);
-	if (!err)
-		err = pool_reserve(w, &w->pl, 64 + sizeof(*ro));
-	if (!err)
-		err = pool_reserve(w, &w->es, n * 4);
+	err = ws_layout_reserve(w, n, &z, &L);
 	if (!err)
 		err = pool_reserve(w, &w->mscr, scr);
 	if (!err && hpos)
 		err = pool_reserve(w, &w->ms, n * 12);
 	if (err)
 		return err;
-	hd_d = (struct sgpu_hdr *)w->hd.d;
-	desc_d = (uint64_t *)w->dsc.d;
-	save_d = (uint32_t *)(w->vs.d + 64);
-	vd_d = w->vs.d + 64 + n * 4;
 	ro = (struct sgpu_rxplan_out *)w->pl.h;
 	ro_d = (struct sgpu_rxplan_out *)w->pl.d;
-	es_d = (uint32_t *)w->es.d;
 
 	memset(&in, 0, sizeof(in));
 	in.n = (uint32_t)n;
@@ -1030,30 +802,28 @@ int dev_rxplanned(struct srtp *s, struct srtp_batch_dev *d, uint32_t *hpos,
 	{
 		/* one launch: parse + end copy + zeroed plan out + comp map */
 		struct sgpu_prologue pro = {
-			es_d, (uint32_t *)ro_d, NULL, (uint32_t)(sizeof(*ro) / 4),
-			0, (uint32_t *)w->cm.d, c0->dev, NULL, NULL, 0, 0, 0, 0,
-			NULL, 0};
+			.end_copy = L.es, .z0 = (uint32_t *)ro_d,
+			.nz0 = (uint32_t)(sizeof(*ro) / 4), .cm_out = L.cm,
+			.cm = c0->dev};
 		err = sgpu_parse_prologue(d->arena, d->arena_size, d->pos,
-					  d->end, hd_d, NULL, (uint32_t)n, 0,
+					  d->end, L.hdr, NULL, (uint32_t)n, 0,
 					  &pro, stream);
 	}
 	if (!err)
-		err = sgpu_plan_rx(&in, hd_d, d->pos, es_d, d->cap,
-				   d->arena_size, desc_d, w->mscr.d, scr, ro_d,
+		err = sgpu_plan_rx(&in, L.hdr, d->pos, L.es, d->cap,
+				   d->arena_size, L.desc, w->mscr.d, scr, ro_d,
 				   stream);
-	if (!err) {
-		/* the general kernels (EALREADY packets: MAC only): AES-CM
-		 * picks the header class from skip[], GCM has one */
-		struct sgpu_compact C = {
-			d->pos, es_d, hd_d, desc_d, NULL,
-			(const uint32_t *)w->cm.d, NULL, 0, (uint32_t)n, vd_d,
-			save_d, &ro_d->nfail, 0, 1,
-			gcm ? &ro_d->fail : ro_d->skip, 0, NULL, NULL};
+	/* the general kernels (EALREADY packets: MAC only): AES-CM picks the
+	 * header class from skip[], GCM has one */
+	C = compact_of(d, &L);
+	C.nfail = &ro_d->nfail;
+	C.uniform = 1;
+	C.guard = gcm ? &ro_d->fail : ro_d->skip;
+	if (!err)
 		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
 				       (int)c0->nr, gcm ? 0 : -1, 0, stream);
-	}
 	if (!err)
-		err = sgpu_plan_rx_commit(ro_d, hd_d, w->mscr.d, es_d, d->pos,
+		err = sgpu_plan_rx_commit(ro_d, L.hdr, w->mscr.d, L.es, d->pos,
 					  d->end, d->err, (uint32_t)n, T, stream);
 	if (!err)
 		err = sgpu_memcpy_d2h(ro, ro_d, sizeof(*ro), stream);
@@ -1082,12 +852,9 @@ int dev_rxplanned(struct srtp *s, struct srtp_batch_dev *d, uint32_t *hpos,
 		count(&g_cnt_misses, ro->nfail);
 		count(&g_cnt_folds, 1);
 		/* AES-CM: one guarded launch per header class, GCM: one */
+		C.undo = 1;
 		for (q = 0; q < (gcm ? 1 : 4) && !err; q++) {
-			struct sgpu_compact C = {
-				d->pos, es_d, hd_d, desc_d, NULL,
-				(const uint32_t *)w->cm.d, NULL, 0, (uint32_t)n,
-				vd_d, save_d, &ro_d->nfail, 1, 1,
-				gcm ? &ro_d->fail : &ro_d->skip[q], 0, NULL, NULL};
+			C.guard = gcm ? &ro_d->fail : &ro_d->skip[q];
 			err = sgpu_run_compact(d->arena, d->arena_size, &C,
 					       c0->mode, (int)c0->nr, q, 0, stream);
 		}
@@ -1180,67 +947,50 @@ int dev_splanned_issue(struct dcall *k)
 	const uint32_t need = prot ? (c0->mode == SGPU_MODE_GCM ? 16u :
 			      (T > 4 ? T : 4u)) : 0u;
 	const size_t scr = sgpu_splan_scratch((uint32_t)n);
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 12,
+		.vs = n * 5 + 64, .cm = 4,
+		.pl = sizeof(struct sgpu_splan_out) + 64, .es = n * 4};
+	struct ws_layout L;
 	struct sgpu_splan_out *po, *po_d;
-	struct sgpu_hdr *hd_d;
-	uint64_t *desc_d;
-	uint32_t *es_d, *save_d, *nfail_d;
-	uint8_t *vd_d;
 	void *stream = d->stream;
 	int err;
 
-	err = pool_reserve(w, &w->hd, n * sizeof(struct sgpu_hdr));
-	if (!err)
-		err = pool_reserve(w, &w->dsc, n * 12);
-	if (!err)
-		err = pool_reserve(w, &w->vs, n * 5 + 64);
-	if (!err)
-		err = pool_reserve(w, &w->cm, 4);
-	if (!err)
-		err = pool_reserve(w, &w->pl, sizeof(struct sgpu_splan_out) + 64);
-	if (!err)
-		err = pool_reserve(w, &w->es, n * 4);
+	err = ws_layout_reserve(w, n, &z, &L);
 	if (!err)
 		err = pool_reserve(w, &w->mscr, scr);
 	if (err)
 		return err;
-	hd_d = (struct sgpu_hdr *)w->hd.d;
-	desc_d = (uint64_t *)w->dsc.d;
-	nfail_d = (uint32_t *)w->vs.d;
-	save_d = (uint32_t *)(w->vs.d + 64);
-	vd_d = w->vs.d + 64 + n * 4;
 	po = (struct sgpu_splan_out *)w->pl.h;
 	po_d = (struct sgpu_splan_out *)w->pl.d;
-	es_d = (uint32_t *)w->es.d;
 
 	splan_in(&k->sin, s, (uint32_t)n, prot, T, need);
 	{
 		struct sgpu_prologue pro = {
-			es_d, nfail_d, (uint32_t *)po_d, 1,
-			(uint32_t)(sizeof(*po) / 4), (uint32_t *)w->cm.d,
-			c0->dev, NULL, NULL, 0, 0, 0, 0, NULL, 0};
+			.end_copy = L.es, .z0 = L.nfail, .z1 = (uint32_t *)po_d,
+			.nz0 = 1, .nz1 = (uint32_t)(sizeof(*po) / 4),
+			.cm_out = L.cm, .cm = c0->dev};
 		k->sin.zeroed = 1;
 		err = sgpu_parse_prologue(d->arena, d->arena_size, d->pos,
-					  d->end, hd_d, NULL, (uint32_t)n, 0,
+					  d->end, L.hdr, NULL, (uint32_t)n, 0,
 					  &pro, stream);
 	}
 	if (!err && k->pred)
 		err = sgpu_gate_pred(k->pred, &po_d->base.fail, stream);
 	if (!err)
-		err = sgpu_splan_rtp(&k->sin, hd_d, d->pos, es_d, d->cap,
-				     d->arena_size, desc_d, w->mscr.d, scr, po_d,
+		err = sgpu_splan_rtp(&k->sin, L.hdr, d->pos, L.es, d->cap,
+				     d->arena_size, L.desc, w->mscr.d, scr, po_d,
 				     stream);
 	if (!err) {
-		struct sgpu_compact C = {
-			d->pos, es_d, hd_d, desc_d, NULL,
-			(const uint32_t *)w->cm.d, NULL, 0, (uint32_t)n, vd_d,
-			save_d, nfail_d, 0, 1, NULL, 0, NULL, NULL};
+		struct sgpu_compact C = compact_of(d, &L);
+		C.uniform = 1;
 		err = run_classes(d->arena, d->arena_size, C, c0,
 				  &po_d->base, prot, stream);
 	}
 	if (!err)
-		err = sgpu_plan_finish(&po_d->base.fail, es_d, d->end, d->err,
+		err = sgpu_plan_finish(&po_d->base.fail, L.es, d->end, d->err,
 				       (uint32_t)n,
-				       prot ? (int32_t)T : -(int32_t)T, nfail_d,
+				       prot ? (int32_t)T : -(int32_t)T, L.nfail,
 				       k->gate, &po_d->base.nfail, NULL, stream);
 	if (!err)
 		err = sgpu_memcpy_d2h(po, po_d, sizeof(*po), stream);
@@ -1261,7 +1011,8 @@ int dev_splanned_finish(struct dcall *k)
 	const struct sgpu_splan_out *po = (const struct sgpu_splan_out *)w->pl.h;
 	struct sgpu_splan_out *po_d = (struct sgpu_splan_out *)w->pl.d;
 	const uint32_t nfail = po->base.nfail;
-	int err;
+	struct ws_layout L;
+	struct sgpu_compact C;
 
 	k->pfail = po->base.fail;
 	if (po->base.fail) {
@@ -1280,43 +1031,21 @@ int dev_splanned_finish(struct dcall *k)
 	count(&g_cnt_misses, nfail);
 	count(&g_cnt_folds, 1);
 	/* a forged packet: undo on the device, fold on the host engine */
-	{
-		struct sgpu_compact C = {
-			d->pos, (uint32_t *)w->es.d, (struct sgpu_hdr *)w->hd.d,
-			(uint64_t *)w->dsc.d, NULL, (const uint32_t *)w->cm.d,
-			NULL, 0, (uint32_t)n, w->vs.d + 64 + n * 4,
-			(uint32_t *)(w->vs.d + 64), (uint32_t *)w->vs.d, 1, 1,
-			NULL, 0, NULL, NULL};
-		err = run_classes(d->arena, d->arena_size, C, c0, &po_d->base,
-				  prot, d->stream);
-	}
-	if (!err)
-		err = sgpu_memcpy_d2d(d->end, w->es.d, n * 4, d->stream);
-	if (!err)
-		err = sgpu_stream_sync(d->stream);
-	return err ? err : -1;
+	ws_layout_get(w, n, &L);
+	C = compact_of(d, &L);
+	C.undo = 1;
+	C.uniform = 1;
+	return undone(run_classes(d->arena, d->arena_size, C, c0, &po_d->base,
+				  prot, d->stream), d, L.es);
 }
 
 /* synchronous: -1 not plannable or folded on the host (nothing
  * modified), else 0 / errno */
 int dev_splanned(int op, struct srtp *s, struct srtp_batch_dev *d)
 {
-	struct dcall k;
-	int err;
-	memset(&k, 0, sizeof(k));
-	k.op = op;
-	k.sessv = &s;
-	k.nsess = 1;
-	k.d = *d;
-	k.w = ws_get();
-	if (!k.w)
-		return ENOMEM;
-	err = dev_splanned_issue(&k);
-	if (!err)
-		err = sgpu_stream_sync(d->stream);
-	if (err)
-		return err;
-	return dev_splanned_finish(&k);
+	uint32_t pf;
+	return dev_call(op, &s, 1, d, 0, dev_splanned_issue,
+			dev_splanned_finish, 0, &pf);
 }
 
 /* the SRTCP plan input of a batch of n packets on session s */
@@ -1377,49 +1106,41 @@ static int dev_lplanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 	const size_t n = d->n;
 	const uint32_t grow = 4u + c0->tag_len + (gcm ? 16u : 0u);
 	const unsigned ns0 = s->nstreams;
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
+		.vs = n * 5 + 64, .cm = 4, .es = n * 4, .es_first = 1};
+	struct ws_layout L;
+	struct fz_layout Z;
+	struct sgpu_compact C;
 	struct srtp_stream old;
 	struct sgpu_rfused R;
 	struct sgpu_plan_out *po, *po_d;
-	uint8_t *vd_d;
-	uint32_t *save_d;
 	void *stream = d->stream;
 	struct ws *w = ws_get();
-	size_t poff;
 	int err;
 
 	if (!w)
 		return ENOMEM;
-	err = pool_reserve(w, &w->hd, n * sizeof(struct sgpu_hdr));
-	if (!err)
-		err = pool_reserve(w, &w->dsc, n * 8);
-	if (!err)
-		err = pool_reserve(w, &w->vs, n * 5 + 64);
-	if (!err)
-		err = pool_reserve(w, &w->cm, 4);
-	if (!err)
-		err = pool_reserve(w, &w->es, n * 4);
+	err = ws_layout_reserve(w, n, &z, &L);
 	if (!err)
 		err = fz_prepare(w, 1, stream);
 	if (err)
 		return err;
-	poff = FZ_HEAD + (size_t)w->fz_par * FZ_SLOT;
-	po = (struct sgpu_plan_out *)(w->fz.h + poff);
-	po_d = (struct sgpu_plan_out *)(w->fz.d + poff);
-	save_d = (uint32_t *)(w->vs.d + 64);
-	vd_d = w->vs.d + 64 + n * 4;
+	Z = fz_layout_get(w, w->fz_par);
+	po = Z.out_h;
+	po_d = Z.out;
 	memset(&R, 0, sizeof(R));
 	rplan_in(&R.in, s, (uint32_t)n, prot);
 	R.pos = d->pos;
 	R.end = d->end;
 	R.cap = d->cap;
 	R.err = d->err;
-	R.es = (uint32_t *)w->es.d;
-	R.hdr = (struct sgpu_hdr *)w->hd.d;
-	R.desc = (uint64_t *)w->dsc.d;
+	R.es = L.es;
+	R.hdr = L.hdr;
+	R.desc = L.desc;
 	R.out = po_d;
-	R.out_next = (struct sgpu_plan_out *)(w->fz.d + FZ_HEAD +
-					      (size_t)(w->fz_par ^ 1) * FZ_SLOT);
-	R.cm_out = (uint32_t *)w->cm.d;
+	R.out_next = Z.out_next;
+	R.cm_out = L.cm;
 	R.comp = c0->dev;
 	R.delta = prot ? (int32_t)grow : -(int32_t)grow;
 	err = sgpu_run_rpplan(d->arena, d->arena_size, &R, stream);
@@ -1428,16 +1149,15 @@ static int dev_lplanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 		return err;
 	}
 	w->fz_par ^= 1;
-	{
-		/* CTR: the lean kernel's SRTCP form (srtp_gpu_tune nolean: the
-		 * general compact kernel) */
-		struct sgpu_compact C = {
-			d->pos, R.es, R.hdr, R.desc, NULL, R.cm_out, NULL, 0,
-			(uint32_t)n, vd_d, save_d, &po_d->nfail, 0,
-			gcm || g_env.nolean ? 1 : 4, &po_d->fail, 1, NULL, NULL};
-		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
-				       (int)c0->nr, gcm ? 0 : 2, prot, stream);
-	}
+	/* CTR: the lean kernel's SRTCP form (srtp_gpu_tune nolean: the
+	 * general compact kernel) */
+	C = compact_of(d, &L);
+	C.nfail = &po_d->nfail;
+	C.uniform = gcm || g_env.nolean ? 1 : 4;
+	C.guard = &po_d->fail;
+	C.rtcp = 1;
+	err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+			       (int)c0->nr, gcm ? 0 : 2, prot, stream);
 	if (!err)   /* the results, guarded by the plan */
 		err = sgpu_plan_results(&po_d->fail, R.es, d->end, d->err,
 					(uint32_t)n, R.delta, stream);
@@ -1465,23 +1185,16 @@ static int dev_lplanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 	count(&g_cnt_misses, po->nfail);
 	count(&g_cnt_folds, 1);
 	/* a forged packet: undo on the device, fold on the host engine */
-	{
-		struct sgpu_compact C = {
-			d->pos, R.es, R.hdr, R.desc, NULL, R.cm_out, NULL, 0,
-			(uint32_t)n, vd_d, save_d, &po_d->nfail, 1, gcm ? 0 : 1,
-			&po_d->fail, 1, NULL, NULL};
-		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
-				       (int)c0->nr, gcm ? 0 : 2, 0, stream);
+	C.undo = 1;
+	C.uniform = gcm ? 0 : 1;
+	err = undone(sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				      (int)c0->nr, gcm ? 0 : 2, 0, stream),
+		     d, L.es);
+	if (err == -1) {
+		s->streams[0] = old;
+		s->nstreams = ns0;
 	}
-	if (!err)
-		err = sgpu_memcpy_d2d(d->end, R.es, n * 4, stream);
-	if (!err)
-		err = sgpu_stream_sync(stream);
-	if (err)
-		return err;
-	s->streams[0] = old;
-	s->nstreams = ns0;
-	return -1;
+	return err;
 }
 
 /*
@@ -1503,86 +1216,59 @@ int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 	const uint32_t T = c0->tag_len;             /* 0 for GCM */
 	const uint32_t grow = 4u + T + (gcm ? 16u : 0u);
 	const unsigned ns0 = s->nstreams;
+	/* hd: the parsed headers | the E || index words */
+	const struct ws_sizes z = {
+		.hd = n * (sizeof(struct sgpu_hdr) + 12), .dsc = n * 12,
+		.vs = n * 5 + 64, .cm = 4,
+		.pl = sizeof(struct sgpu_plan_out) + 64, .es = n * 4};
+	struct ws_layout L;
+	struct sgpu_compact C;
 	struct srtp_stream old;
 	struct sgpu_rplan_in in;
 	struct sgpu_plan_out *po, *po_d;
-	struct sgpu_hdr *hd_d;
-	uint64_t *desc_d;
-	uint32_t *es_d, *save_d, *nfail_d, *eix_d, nfail, cm = c0->dev;
-	uint8_t *vd_d;
+	uint32_t *eix_d, nfail;
 	void *stream = d->stream;
 	struct ws *w = ws_get();
 	int err;
 
 	if (!w)
 		return ENOMEM;
-	err = pool_reserve(w, &w->hd, n * (sizeof(struct sgpu_hdr) + 12));
-	if (!err)
-		err = pool_reserve(w, &w->dsc, n * 12);
-	if (!err)
-		err = pool_reserve(w, &w->vs, n * 5 + 64);
-	if (!err)
-		err = pool_reserve(w, &w->cm, 4);
-	if (!err)
-		err = pool_reserve(w, &w->pl, sizeof(struct sgpu_plan_out) + 64);
-	if (!err)
-		err = pool_reserve(w, &w->es, n * 4);
+	err = ws_layout_reserve(w, n, &z, &L);
 	if (err)
 		return err;
-	hd_d = (struct sgpu_hdr *)w->hd.d;
 	eix_d = (uint32_t *)(w->hd.d + n * sizeof(struct sgpu_hdr));
-	desc_d = (uint64_t *)w->dsc.d;
-	nfail_d = (uint32_t *)w->vs.d;
-	save_d = (uint32_t *)(w->vs.d + 64);
-	vd_d = w->vs.d + 64 + n * 4;
 	po = (struct sgpu_plan_out *)w->pl.h;
 	po_d = (struct sgpu_plan_out *)w->pl.d;
-	es_d = (uint32_t *)w->es.d;
 
-	memset(&in, 0, sizeof(in));
-	in.n = (uint32_t)n;
-	in.prot = (uint32_t)prot;
-	in.ssrc_any = !s->nstreams;
-	in.ssrc = s->nstreams ? s->streams[0].ssrc : 0;
-	in.rtcp_index = s->nstreams ? s->streams[0].rtcp_index : 0;
-	in.lix = s->nstreams ? s->streams[0].replay_rtcp.lix : 0;
-	in.bitmap = s->nstreams ? s->streams[0].replay_rtcp.bitmap : 0;
-	in.tag = T;
-	in.gcm = (uint32_t)gcm;
-	in.hmac = (uint32_t)c0->has_hmac;
-	in.encrypted = (uint32_t)(gcm ? c0->encrypted : c0->has_aes);
-	in.need = grow;
-	in.maxlen = SGPU_CACHED_MAX(c0->mode);
+	rplan_in(&in, s, (uint32_t)n, prot);
 	{
 		/* parse (+ E || index words) + end copy + zeroed counters and
 		 * plan + comp map, one launch */
 		struct sgpu_prologue pro = {
-			es_d, nfail_d, (uint32_t *)po_d, 1,
-			(uint32_t)(sizeof(*po) / 4), (uint32_t *)w->cm.d, cm, NULL, NULL,
-			0, 0, 0, 0, NULL, 0};
+			.end_copy = L.es, .z0 = L.nfail, .z1 = (uint32_t *)po_d,
+			.nz0 = 1, .nz1 = (uint32_t)(sizeof(*po) / 4),
+			.cm_out = L.cm, .cm = c0->dev};
 		err = sgpu_parse_prologue(d->arena, d->arena_size, d->pos,
-					  d->end, hd_d, prot ? NULL : eix_d,
+					  d->end, L.hdr, prot ? NULL : eix_d,
 					  (uint32_t)n, 1, &pro, stream);
 	}
 	if (!err)
-		err = sgpu_plan_rtcp(&in, hd_d, eix_d, d->pos, es_d, d->cap,
-				     d->arena_size, desc_d, po_d, stream);
-	if (!err) {
-		/* CTR: the lean kernel's SRTCP form (srtp_gpu_tune nolean:
-		 * the general compact kernel) */
-		struct sgpu_compact C = {
-			d->pos, es_d, hd_d, desc_d, NULL,
-			(const uint32_t *)w->cm.d, NULL, 0, (uint32_t)n, vd_d,
-			save_d, nfail_d, 0, gcm || g_env.nolean ? 1 : 4,
-			gcm ? &po_d->fail : &po_d->skip[2], 1, NULL, NULL};
+		err = sgpu_plan_rtcp(&in, L.hdr, eix_d, d->pos, L.es, d->cap,
+				     d->arena_size, L.desc, po_d, stream);
+	/* CTR: the lean kernel's SRTCP form (srtp_gpu_tune nolean: the
+	 * general compact kernel) */
+	C = compact_of(d, &L);
+	C.uniform = gcm || g_env.nolean ? 1 : 4;
+	C.guard = gcm ? &po_d->fail : &po_d->skip[2];
+	C.rtcp = 1;
+	if (!err)
 		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
 				       (int)c0->nr, gcm ? 0 : 2, prot, stream);
-	}
 	if (!err)
-		err = sgpu_plan_finish(&po_d->fail, es_d, d->end, d->err,
+		err = sgpu_plan_finish(&po_d->fail, L.es, d->end, d->err,
 				       (uint32_t)n,
 				       prot ? (int32_t)grow : -(int32_t)grow,
-				       nfail_d, NULL, &po_d->nfail, NULL, stream);
+				       L.nfail, NULL, &po_d->nfail, NULL, stream);
 	if (!err)
 		err = sgpu_memcpy_d2h(po, po_d, sizeof(*po), stream);
 	if (!err)
@@ -1595,42 +1281,22 @@ int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 		return -1;
 	}
 	count(&g_cnt_rplans, 1);
-	/* the stream (stream.c:45-67) and its SRTCP state after the batch */
-	if (!s->nstreams) {
-		memset(&s->streams[0], 0, sizeof(s->streams[0]));
-		s->streams[0].ssrc = po->ssrc0;
-		s->nstreams = 1;
-	}
-	old = s->streams[0];
-	if (prot)
-		s->streams[0].rtcp_index =
-			(s->streams[0].rtcp_index + (uint32_t)n) & 0x7fffffffu;
-	else if (c0->has_hmac)
-		s->streams[0].replay_rtcp =
-			plan_replay(&s->streams[0].replay_rtcp, po->tail_ix, n);
+	rplan_apply(s, po, prot, n, &old);
 	if (!nfail)
 		return 0;
 	count(&g_cnt_misses, nfail);
 	count(&g_cnt_folds, 1);
 	/* a forged packet: undo on the device, fold on the host engine */
-	{
-		struct sgpu_compact C = {
-			d->pos, es_d, hd_d, desc_d, NULL,
-			(const uint32_t *)w->cm.d, NULL, 0, (uint32_t)n, vd_d,
-			save_d, nfail_d, 1, gcm ? 0 : 1,
-			gcm ? &po_d->fail : &po_d->skip[2], 1, NULL, NULL};
-		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
-				       (int)c0->nr, gcm ? 0 : 2, 0, stream);
+	C.undo = 1;
+	C.uniform = gcm ? 0 : 1;
+	err = undone(sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				      (int)c0->nr, gcm ? 0 : 2, 0, stream),
+		     d, L.es);
+	if (err == -1) {
+		s->streams[0] = old;
+		s->nstreams = ns0;
 	}
-	if (!err)
-		err = sgpu_memcpy_d2d(d->end, es_d, n * 4, stream);
-	if (!err)
-		err = sgpu_stream_sync(stream);
-	if (err)
-		return err;
-	s->streams[0] = old;
-	s->nstreams = ns0;
-	return -1;
+	return err;
 }
 
 /*
@@ -1651,13 +1317,13 @@ static int mfold(struct dcall *k, int phase, const uint32_t *nfail,
 	struct ws *w = k->w;
 	const size_t n = d->n;
 	struct sgpu_mplan_in in;
+	struct ws_layout L;
+	ws_layout_get(w, n, &L);
 	memset(&in, 0, sizeof(in));
 	in.n = (uint32_t)n;
 	in.nsess = (uint32_t)k->nsess;
-	return sgpu_mfold_rtp(phase, nfail, &in, (const struct sgpu_hdr *)w->hd.d,
-			      d->sess, (const uint64_t *)w->dsc.d,
-			      w->vs.d + 64 + n * 4, (const uint32_t *)w->es.d,
-			      d->pos, d->end, d->err,
+	return sgpu_mfold_rtp(phase, nfail, &in, L.hdr, d->sess, L.desc,
+			      L.verdict, L.es, d->pos, d->end, d->err,
 			      k->sessv[0]->rtp.mode == SGPU_MODE_GCM, sin_d,
 			      sout_d, w->mscr.d, scr,
 			      (uint32_t *)(w->pl.d + k->foff + 64),
@@ -1696,20 +1362,17 @@ static int dev_bplanned_issue(struct dcall *k, uint32_t bshift, uint32_t nb,
 	uint32_t *cm_h;
 	void *stream = d->stream;
 	const int times = g_env.times;
+	/* pl: plan out | fold out */
+	const size_t foff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
+		.vs = n * 9 + 72, .cm = nsess * 4, .pl = foff + 64,
+		.es = n * 4};
+	struct ws_layout L;
 	int err;
 
-	err = pool_reserve(w, &w->hd, n * sizeof(struct sgpu_hdr));
-	if (!err)
-		err = pool_reserve(w, &w->dsc, n * 8);
-	if (!err)   /* nfail | save | verdict | forged list */
-		err = pool_reserve(w, &w->vs, n * 9 + 72);
-	if (!err)
-		err = pool_reserve(w, &w->cm, nsess * 4);
-	k->foff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
-	if (!err)   /* plan out | fold out */
-		err = pool_reserve(w, &w->pl, k->foff + 64);
-	if (!err)
-		err = pool_reserve(w, &w->es, n * 4);
+	k->foff = foff;
+	err = ws_layout_reserve(w, n, &z, &L);
 	if (!err)   /* uploads | need */
 		err = pool_reserve(w, &w->ms,
 				   nsess * (sizeof(struct sgpu_sstate) + 1));
@@ -1749,9 +1412,9 @@ static int dev_bplanned_issue(struct dcall *k, uint32_t bshift, uint32_t nb,
 	B->posw = d->pos;
 	B->endw = d->end;
 	B->err = d->err;
-	B->es = (uint32_t *)w->es.d;
-	B->hdr = (struct sgpu_hdr *)w->hd.d;
-	B->desc = (uint64_t *)w->dsc.d;
+	B->es = L.es;
+	B->hdr = L.hdr;
+	B->desc = L.desc;
 	p = w->bp.d;
 	B->ticket = (uint32_t *)p;
 	B->obins = (uint32_t *)(p + 64);
@@ -1774,10 +1437,9 @@ static int dev_bplanned_issue(struct dcall *k, uint32_t bshift, uint32_t nb,
 	B->fo = (struct sgpu_fold_out *)(w->pl.d + k->foff);
 	B->pred = k->pred;
 	B->gate = k->gate;
-	B->nfail = (uint32_t *)w->vs.d;
-	B->verdict = w->vs.d + 64 + n * 4;
-	B->flist = !prot && !gcm && k->devfold ?
-		   (uint32_t *)(w->vs.d + ((64 + n * 5 + 3) & ~(size_t)3)) : NULL;
+	B->nfail = L.nfail;
+	B->verdict = L.verdict;
+	B->flist = !prot && !gcm && k->devfold ? L.flist : NULL;
 	/* parse, checks, bucket slots: no session state needed, so it runs
 	 * while the host walks the sessions */
 	err = sgpu_bplan_scatter(d->arena, d->arena_size, B, stream);
@@ -1833,12 +1495,11 @@ static int dev_bplanned_issue(struct dcall *k, uint32_t bshift, uint32_t nb,
 	if (!err) {
 		/* the crypto launches behind the plan's guards (the class
 		 * guards skip[] and the fail word), in its order */
-		struct sgpu_compact C = {
-			d->pos, B->es, B->hdr, B->desc, d->sess,
-			(const uint32_t *)w->cm.d, B->order, 0, (uint32_t)n,
-			(uint8_t *)B->verdict, (uint32_t *)(w->vs.d + 64),
-			B->nfail, 0, 0, NULL, 0, (uint32_t *)B->flist,
-			&B->out->fail};
+		struct sgpu_compact C = compact_of(d, &L);
+		C.sess = d->sess;
+		C.idx = B->order;
+		C.flist = (uint32_t *)B->flist;
+		C.gfail = &B->out->fail;
 		err = run_classes(d->arena, d->arena_size, C, c0,
 				  B->out, prot, stream);
 	}
@@ -1884,10 +1545,17 @@ int dev_mplanned_issue(struct dcall *k)
 	struct sgpu_fold_out *fo_d;
 	struct sgpu_sstate *up_h, *up_d, *sin_d, *sout_d;
 	struct sgpu_mplan_in in;
+	/* pl: plan out | fold out | fold scratch (multi-session fold) */
+	const size_t foff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 12,
+		.vs = n * 9 + 72, .cm = nsess * 4,
+		.pl = foff + 64 + sgpu_mfold_scratch((uint32_t)n), .es = n * 4};
+	struct ws_layout L;
 	struct sgpu_hdr *hd_d;
 	uint64_t *desc_d;
-	uint32_t *es_d, *save_d, *nfail_d, *cm_h, *order_d, bits = 1;
-	uint8_t *vd_d, *need_h, *need_d;
+	uint32_t *es_d, *nfail_d, *cm_h, *order_d, bits = 1;
+	uint8_t *need_h, *need_d;
 	size_t scr;
 	void *stream = d->stream;
 	const int times = g_env.times;
@@ -1896,20 +1564,8 @@ int dev_mplanned_issue(struct dcall *k)
 	while (bits < 32 && ((size_t)1 << bits) < nsess)
 		bits++;
 	scr = sgpu_mplan_scratch((uint32_t)n, (uint32_t)nsess);
-	err = pool_reserve(w, &w->hd, n * sizeof(struct sgpu_hdr));
-	if (!err)
-		err = pool_reserve(w, &w->dsc, n * 12);
-	if (!err)   /* verdict | save | nfail | forged list */
-		err = pool_reserve(w, &w->vs, n * 9 + 72);
-	if (!err)
-		err = pool_reserve(w, &w->cm, nsess * 4);
-	/* pl: plan out | fold out | fold scratch (multi-session fold) */
-	k->foff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
-	if (!err)
-		err = pool_reserve(w, &w->pl, k->foff + 64 +
-				   sgpu_mfold_scratch((uint32_t)n));
-	if (!err)
-		err = pool_reserve(w, &w->es, n * 4);
+	k->foff = foff;
+	err = ws_layout_reserve(w, n, &z, &L);
 	if (!err)
 		err = pool_reserve(w, &w->ms,
 				   nsess * (3 * sizeof(struct sgpu_sstate) + 1));
@@ -1918,14 +1574,12 @@ int dev_mplanned_issue(struct dcall *k)
 		err = pool_reserve(w, &w->mscr, scr + n * 4 + (n / 256 + 1) * 4);
 	if (err)
 		return err;
-	hd_d = (struct sgpu_hdr *)w->hd.d;
-	desc_d = (uint64_t *)w->dsc.d;
-	nfail_d = (uint32_t *)w->vs.d;
-	save_d = (uint32_t *)(w->vs.d + 64);
-	vd_d = w->vs.d + 64 + n * 4;
+	hd_d = L.hdr;
+	desc_d = L.desc;
+	nfail_d = L.nfail;
+	es_d = L.es;
 	po = (struct sgpu_plan_out *)w->pl.h;
 	po_d = (struct sgpu_plan_out *)w->pl.d;
-	es_d = (uint32_t *)w->es.d;
 	cm_h = (uint32_t *)w->cm.h;
 	/* ms: st_in | st_out | uploads | need (device; host: the uploads) */
 	sin_d = (struct sgpu_sstate *)w->ms.d;
@@ -1943,20 +1597,18 @@ int dev_mplanned_issue(struct dcall *k)
 		/* zeroes the plan out too (k_mp_iota ORs into it) and the
 		 * counting grouping's per-session counters */
 		const int radix = k->radix || g_env.mpradix || nsess > 65536;
-		struct sgpu_prologue pro = {es_d, nfail_d, (uint32_t *)po_d, 1,
-					    (uint32_t)(sizeof(*po) / 4), NULL, 0,
-					    (uint32_t *)in.wchk, d->cap,
-					    (uint32_t)prot, T,
-					    prot ? (gcm ? 16u : (T > 4 ? T : 4u))
-						 : 0u,
-					    SGPU_CACHED_MAX(c0->mode),
-					    radix ? NULL :
-					    sgpu_mplan_counters(w->mscr.d,
-								(uint32_t)n,
-								(uint32_t)nsess),
-					    radix ? 0u :
-					    sgpu_mplan_counter_words(
-						    (uint32_t)nsess)};
+		struct sgpu_prologue pro = {
+			.end_copy = es_d, .z0 = nfail_d, .z1 = (uint32_t *)po_d,
+			.nz0 = 1, .nz1 = (uint32_t)(sizeof(*po) / 4),
+			.wchk = (uint32_t *)in.wchk, .cap = d->cap,
+			.prot = (uint32_t)prot, .tag = T,
+			.need = prot ? (gcm ? 16u : (T > 4 ? T : 4u)) : 0u,
+			.maxlen = SGPU_CACHED_MAX(c0->mode),
+			.z2 = radix ? NULL :
+			      sgpu_mplan_counters(w->mscr.d, (uint32_t)n,
+						  (uint32_t)nsess),
+			.nz2 = radix ? 0u :
+			       sgpu_mplan_counter_words((uint32_t)nsess)};
 		in.radix = (uint32_t)radix;
 		in.cnt_zeroed = !radix;
 		err = sgpu_parse_prologue(d->arena, d->arena_size, d->pos,
@@ -2031,13 +1683,10 @@ int dev_mplanned_issue(struct dcall *k)
 	if (!err) {
 		/* unprotect (CTR): forged packets are listed and restored
 		 * behind the kernel, for the device fold (dev_mplanned_finish) */
-		uint32_t *flist_d = (uint32_t *)(w->vs.d +
-						 ((64 + n * 5 + 3) & ~(size_t)3));
-		struct sgpu_compact C = {
-			d->pos, es_d, hd_d, desc_d, d->sess,
-			(const uint32_t *)w->cm.d, order_d, 0, (uint32_t)n,
-			vd_d, save_d, nfail_d, 0, 0, NULL, 0,
-			!prot && !gcm && !g_env.nodevfold ? flist_d : NULL, NULL};
+		struct sgpu_compact C = compact_of(d, &L);
+		C.sess = d->sess;
+		C.idx = order_d;
+		C.flist = !prot && !gcm && !g_env.nodevfold ? L.flist : NULL;
 		err = run_classes(d->arena, d->arena_size, C, c0,
 				  po_d, prot, stream);
 	}
@@ -2084,15 +1733,9 @@ int dev_mplanned_finish(struct dcall *k)
 	const size_t n = d->n;
 	struct sgpu_plan_out *po = (struct sgpu_plan_out *)w->pl.h;
 	struct sgpu_plan_out *po_d = (struct sgpu_plan_out *)w->pl.d;
-	struct sgpu_hdr *hd_d = (struct sgpu_hdr *)w->hd.d;
-	uint64_t *desc_d = (uint64_t *)w->dsc.d;
-	uint32_t *nfail_d = (uint32_t *)w->vs.d;
-	uint32_t *save_d = (uint32_t *)(w->vs.d + 64);
-	uint8_t *vd_d = w->vs.d + 64 + n * 4;
-	uint32_t *es_d = (uint32_t *)w->es.d;
-	void *stream = d->stream;
 	uint32_t nfail = po->nfail;
-	int err;
+	struct ws_layout L;
+	struct sgpu_compact C;
 
 	k->pfail = po->fail;
 	if (g_env.times)
@@ -2127,47 +1770,22 @@ int dev_mplanned_finish(struct dcall *k)
 		}
 	}
 	count(&g_cnt_folds, 1);
-	/* undo on the device, fold on the host engine */
-	{
-		struct sgpu_compact C = {
-			d->pos, es_d, hd_d, desc_d, d->sess,
-			(const uint32_t *)w->cm.d, NULL, 0, (uint32_t)n, vd_d,
-			save_d, nfail_d, 1, 0, NULL, 0, NULL, NULL};
-		err = run_classes(d->arena, d->arena_size, C, c0,
-				  po_d, prot, stream);
-	}
-	if (!err)
-		err = sgpu_memcpy_d2d(d->end, es_d, n * 4, stream);
-	if (!err)
-		err = sgpu_stream_sync(stream);
-	if (err)
-		return err;
-	return -1;      /* resident states untouched: the host folds */
+	/* undo on the device, fold on the host engine (the resident states
+	 * are untouched) */
+	ws_layout_get(w, n, &L);
+	C = compact_of(d, &L);
+	C.sess = d->sess;
+	C.undo = 1;
+	return undone(run_classes(d->arena, d->arena_size, C, c0, po_d, prot,
+				  d->stream), d, L.es);
 }
 
 /* synchronous: -1 not plannable (nothing modified), else 0 / errno */
 int dev_mplanned_(int op, struct srtp **sessv, size_t nsess,
 			 struct srtp_batch_dev *d, int radix, uint32_t *pfail)
 {
-	struct dcall k;
-	int err;
-	memset(&k, 0, sizeof(k));
-	k.op = op;
-	k.sessv = sessv;
-	k.nsess = nsess;
-	k.d = *d;
-	k.radix = radix;
-	k.w = ws_get();
-	if (!k.w)
-		return ENOMEM;
-	err = dev_mplanned_issue(&k);
-	if (!err)
-		err = sgpu_stream_sync(d->stream);
-	if (err)
-		return err;
-	err = dev_mplanned_finish(&k);
-	*pfail = k.pfail;
-	return err;
+	return dev_call(op, sessv, nsess, d, radix, dev_mplanned_issue,
+			dev_mplanned_finish, 0, pfail);
 }
 
 /* a session with more than SGPU_MP_SEGMAX packets (SPF_SEG): re-planned

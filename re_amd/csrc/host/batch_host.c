@@ -813,11 +813,10 @@ static int run_mplanned(int op, struct srtp **sessv, size_t nsess,
 	struct sgpu_plan_out *po = (struct sgpu_plan_out *)w->pl.h;
 	struct sgpu_plan_out *po_d = (struct sgpu_plan_out *)w->pl.d;
 	uint32_t *up_h = (uint32_t *)w->up.h, *up_d = (uint32_t *)w->up.d;
-	struct sgpu_hdr *hd_d = (struct sgpu_hdr *)w->hd.d;
-	uint64_t *desc_d = (uint64_t *)w->dsc.d;
-	uint32_t *nfail_d = (uint32_t *)w->vs.d;
-	uint32_t *save_d = (uint32_t *)(w->vs.d + 64);
-	uint8_t *vd_d = w->vs.d + 64 + n * 4;
+	struct ws_layout L;     /* over the pools run_fast reserved */
+	struct sgpu_hdr *hd_d;
+	uint64_t *desc_d;
+	uint32_t *nfail_d;
 	struct sgpu_sstate *sin_h, *sin_d, *sout_h, *sout_d;
 	uint32_t *order_d;
 	struct sgpu_mplan_in in;
@@ -825,6 +824,10 @@ static int run_mplanned(int op, struct srtp **sessv, size_t nsess,
 	uint32_t bits = 1;
 	int err, capok = 1, q;
 
+	ws_layout_get(w, n, &L);
+	hd_d = L.hdr;
+	desc_d = L.desc;
+	nfail_d = L.nfail;
 	while (bits < 32 && ((size_t)1 << bits) < nsess)
 		bits++;
 	/* the original windows first: the caller restores them from up_h on
@@ -878,9 +881,10 @@ static int run_mplanned(int op, struct srtp **sessv, size_t nsess,
 			capok &= (uint64_t)b->end[i] + need <= b->cap[i];
 	if (!err && capok) {
 		struct sgpu_compact C = {
-			up_d, up_d + n, hd_d, desc_d, up_d + 2 * n,
-			(const uint32_t *)w->cm.d, order_d, 0, (uint32_t)n,
-			vd_d, save_d, nfail_d, 0, 0, NULL, 0, NULL, NULL};
+			.pos = up_d, .end = up_d + n, .hdr = hd_d, .desc = desc_d,
+			.sess = up_d + 2 * n, .compmap = L.cm, .idx = order_d,
+			.n = (uint32_t)n, .verdict = L.verdict, .save = L.save,
+			.nfail = nfail_d};
 		err = run_classes(b->arena, b->arena_size, C, c0,
 				  po_d, prot, stream);
 	}
@@ -940,12 +944,18 @@ static int run_fast(int op, struct srtp **sessv, size_t nsess,
 	struct fscan FT[1];
 	struct flaunch *fl = NULL;
 	size_t nfl = 0, i, k;
+	/* dsc: descriptors | class lists; pl: plan out | plan scratch */
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 12,
+		.vs = n * 5 + 64, .cm = nsess * 4,
+		.pl = sizeof(struct sgpu_plan_out) + (n / 256 + 8) * 4};
+	struct ws_layout L;
+	struct sgpu_compact C;
 	uint32_t *up_h, *up_d, *cm_h;
 	struct sgpu_hdr *hd_d;
 	uint64_t *desc_d;
 	uint32_t *idx_h, *idx_d;
-	uint8_t *vd_d;
-	uint32_t *save_d, *nfail_d, nfail = 0;
+	uint32_t *nfail_d, nfail = 0;
 	void *stream, *entry_ev = NULL;
 	struct ws *w;
 	int err = 0, parsed = 0, planned = 0;
@@ -983,16 +993,7 @@ static int run_fast(int op, struct srtp **sessv, size_t nsess,
 
 	err = pool_reserve(w, &w->up, n * 12);
 	if (!err)
-		err = pool_reserve(w, &w->hd, n * sizeof(struct sgpu_hdr));
-	if (!err)
-		err = pool_reserve(w, &w->dsc, n * 12);
-	if (!err)
-		err = pool_reserve(w, &w->vs, n * 5 + 64);
-	if (!err)
-		err = pool_reserve(w, &w->cm, nsess * 4);
-	if (!err)
-		err = pool_reserve(w, &w->pl, sizeof(struct sgpu_plan_out) +
-				   (n / 256 + 8) * 4);
+		err = ws_layout_reserve(w, n, &z, &L);
 	if (err)
 		return err;
 	if (w->nev < nch) {
@@ -1013,14 +1014,18 @@ static int run_fast(int op, struct srtp **sessv, size_t nsess,
 
 	up_h = (uint32_t *)w->up.h;
 	up_d = (uint32_t *)w->up.d;
-	hd_d = (struct sgpu_hdr *)w->hd.d;
-	desc_d = (uint64_t *)w->dsc.d;
+	hd_d = L.hdr;
+	desc_d = L.desc;
 	idx_h = (uint32_t *)(w->dsc.h + n * 8);
 	idx_d = (uint32_t *)(w->dsc.d + n * 8);
-	nfail_d = (uint32_t *)(w->vs.d);
-	save_d = (uint32_t *)(w->vs.d + 64);
-	vd_d = w->vs.d + 64 + n * 4;
+	nfail_d = L.nfail;
 	cm_h = (uint32_t *)w->cm.h;
+	/* the crypto launches read the staged windows (w->up), not the
+	 * caller's: pos | end | sess */
+	C = (struct sgpu_compact){
+		.pos = up_d, .end = up_d + n, .hdr = hd_d, .desc = desc_d,
+		.compmap = L.cm, .n = (uint32_t)n, .verdict = L.verdict,
+		.save = L.save, .nfail = nfail_d};
 	for (k = 0; k < nsess; k++)
 		cm_h[k] = 2u * sessv[k]->slot;          /* comp[0] = RTP */
 
@@ -1093,11 +1098,9 @@ static int run_fast(int op, struct srtp **sessv, size_t nsess,
 			for (i = 0; i < n; i++)
 				capok &= (uint64_t)b->end[i] + need <= b->cap[i];
 		if (!err && capok) {
-			struct sgpu_compact C = {
-				up_d, up_d + n, hd_d, desc_d, NULL,
-				(const uint32_t *)w->cm.d, NULL, 0,
-				(uint32_t)n, vd_d, save_d, nfail_d, 0, 1, NULL, 0, NULL, NULL};
-			err = run_classes(b->arena, b->arena_size, C, c0,
+			struct sgpu_compact P = C;
+			P.uniform = 1;
+			err = run_classes(b->arena, b->arena_size, P, c0,
 					  po_d, prot, stream);
 		}
 		if (!err)
@@ -1303,14 +1306,13 @@ static int run_fast(int op, struct srtp **sessv, size_t nsess,
 					      (o - a) * 4, stream);
 		}
 		for (q = nfl - (nz == 1 ? 1 : nz); q < nfl && !err; q++) {
-			struct sgpu_compact C = {
-				up_d, up_d + n, hd_d, desc_d,
-				b->sess ? up_d + 2 * n : NULL,
-				(const uint32_t *)w->cm.d,
-				fl[q].has_idx ? idx_d : NULL, fl[q].base,
-				fl[q].n, vd_d, save_d, nfail_d, 0, nsess == 1,
-				NULL, 0, NULL, NULL};
-			err = sgpu_run_compact(b->arena, b->arena_size, &C,
+			struct sgpu_compact Q = C;
+			Q.sess = b->sess ? up_d + 2 * n : NULL;
+			Q.idx = fl[q].has_idx ? idx_d : NULL;
+			Q.base = fl[q].base;
+			Q.n = fl[q].n;
+			Q.uniform = nsess == 1;
+			err = sgpu_run_compact(b->arena, b->arena_size, &Q,
 					       c0->mode, (int)c0->nr,
 					       (int)fl[q].shift, prot, stream);
 		}
@@ -1336,19 +1338,19 @@ static int run_fast(int op, struct srtp **sessv, size_t nsess,
 		count(&g_cnt_folds, 1);
 		/* speculation missed: undo and fold exactly */
 		for (k = 0; k < nfl && !err; k++) {
-			struct sgpu_compact C = {
-				up_d, up_d + n, hd_d, desc_d,
-				b->sess ? up_d + 2 * n : NULL,
-				(const uint32_t *)w->cm.d,
-				fl[k].has_idx ? idx_d : NULL, fl[k].base,
-				fl[k].n, vd_d, save_d, nfail_d, 1, nsess == 1,
-				!planned ? NULL :
-				c0->mode == SGPU_MODE_GCM ?
-				&((struct sgpu_plan_out *)w->pl.d)->fail :
-				&((struct sgpu_plan_out *)w->pl.d)->
-					  skip[fl[k].shift], 0, NULL, NULL};
-			C.uniform = planned != 2 && nsess == 1;
-			err = sgpu_run_compact(b->arena, b->arena_size, &C,
+			struct sgpu_plan_out *po_d =
+				(struct sgpu_plan_out *)w->pl.d;
+			struct sgpu_compact U = C;
+			U.sess = b->sess ? up_d + 2 * n : NULL;
+			U.idx = fl[k].has_idx ? idx_d : NULL;
+			U.base = fl[k].base;
+			U.n = fl[k].n;
+			U.undo = 1;
+			U.uniform = planned != 2 && nsess == 1;
+			U.guard = !planned ? NULL :
+				  c0->mode == SGPU_MODE_GCM ? &po_d->fail :
+				  &po_d->skip[fl[k].shift];
+			err = sgpu_run_compact(b->arena, b->arena_size, &U,
 					       c0->mode, (int)c0->nr,
 					       (int)fl[k].shift, prot, stream);
 		}

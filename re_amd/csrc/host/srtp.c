@@ -122,7 +122,7 @@ uint64_t g_cnt_rejects;  /* device plans rejected */
 uint64_t g_cnt_devfolds; /* verdicts folded on the device */
 uint64_t g_cnt_splans;   /* per-stream device plans accepted */
 uint64_t g_cnt_fused;    /* batches planned inside the crypto launch
-				   (dev_fused), accepted */
+				   (fz_issue, kind 1), accepted */
 uint64_t g_cnt_dplans;   /* single-stream planner launches (k_plan_*,
 				   GCM and noplanfuse), accepted */
 uint64_t g_cnt_mplans;   /* multi-session device plans accepted */
@@ -155,7 +155,8 @@ uint64_t g_cnt_gated;    /* asynchronous calls gated behind one the
 uint64_t g_cnt_small, g_ns_small_launch, g_ns_small_sync, g_ns_mbufs;
 /* pc_run_fused: host time before the launch and after the sync (ns) */
 uint64_t g_ns_fused_prep, g_ns_fused_post;
-/* synchronous one-stream device calls (dev_fused): host time to issue,
+/* synchronous one-stream calls planned inside the crypto launch (dev_call,
+ * timed): host time to issue,
  * waiting for the stream, completing (ns) */
 uint64_t g_cnt_sync_calls, g_ns_sync_issue, g_ns_sync_wait, g_ns_sync_finish;
 

@@ -233,8 +233,9 @@ struct ws {
 				   (on the side stream w->stream) */
 	size_t nev;
 	struct ulogv ulog[1];   /* stream-state undo log */
-	/* single-stream batches planned inside the crypto launch
-	 * (dev_fused): ticket | pad | plan out x2 | look-back words */
+	/* single-stream batches planned inside the crypto launch or by
+	 * the one-launch planner (batch_dev.c fz_issue): ticket | pad |
+	 * (plan out, fold out) x2 | look-back words */
 	struct pool fz;
 	uint8_t *fz_d;          /* fz.d the state below belongs to */
 	uint32_t fz_tbase;      /* the next launch's first ticket */
@@ -322,6 +323,71 @@ struct ws *ws_new(void);
 struct ws *ws_get(void);
 int pool_reserve(struct ws *w, struct pool *p, size_t bytes);
 int idx_reserve(struct ws *w, size_t n);
+
+/*
+ * What a device-side batch of n packets uses of the workspace pools (device
+ * pointers).  vs: the miss counter, padded to 64 bytes | save, n words |
+ * verdict, n bytes, padded to a word | the forged list, n words.
+ */
+struct ws_layout {
+	struct sgpu_hdr *hdr;   /* hd */
+	uint64_t *desc;         /* dsc */
+	uint32_t *nfail;        /* vs */
+	uint32_t *save;
+	uint8_t *verdict;
+	uint32_t *flist;        /* NULL: vs was reserved without the list */
+	uint32_t *es;           /* es: the original ends */
+	uint32_t *cm;           /* cm: session -> comp index */
+};
+
+/* bytes each pool must hold (0: not used by the call); reserved in the
+ * order hd, dsc, vs, cm, then pl and es (es_first: es before pl) */
+struct ws_sizes {
+	size_t hd, dsc, vs, cm, pl, es;
+	int es_first;
+};
+
+/* the layout over pools already reserved (no forged list) */
+static inline void ws_layout_get(const struct ws *w, size_t n,
+				 struct ws_layout *L)
+{
+	L->hdr = (struct sgpu_hdr *)w->hd.d;
+	L->desc = (uint64_t *)w->dsc.d;
+	L->nfail = (uint32_t *)w->vs.d;
+	L->save = (uint32_t *)(w->vs.d + 64);
+	L->verdict = w->vs.d + 64 + n * 4;
+	L->flist = NULL;
+	L->es = (uint32_t *)w->es.d;
+	L->cm = (uint32_t *)w->cm.d;
+}
+
+/* reserve the pools of a call and lay it out; 0 / errno */
+static inline int ws_layout_reserve(struct ws *w, size_t n,
+				    const struct ws_sizes *z,
+				    struct ws_layout *L)
+{
+	const size_t fl = (64 + n * 5 + 3) & ~(size_t)3;
+	int err = pool_reserve(w, &w->hd, z->hd);
+	if (!err)
+		err = pool_reserve(w, &w->dsc, z->dsc);
+	if (!err)
+		err = pool_reserve(w, &w->vs, z->vs);
+	if (!err)
+		err = pool_reserve(w, &w->cm, z->cm);
+	if (!err)
+		err = pool_reserve(w, z->es_first ? &w->es : &w->pl,
+				   z->es_first ? z->es : z->pl);
+	if (!err)
+		err = pool_reserve(w, z->es_first ? &w->pl : &w->es,
+				   z->es_first ? z->pl : z->es);
+	if (err)
+		return err;
+	ws_layout_get(w, n, L);
+	if (z->vs >= fl + n * 4)
+		L->flist = (uint32_t *)(w->vs.d + fl);
+	return 0;
+}
+
 size_t small_fits(const struct engine *E);
 void collect_rec(struct rec *r, uint8_t v, uint32_t save);
 void srv_stop(struct ws *w);
@@ -355,7 +421,8 @@ struct dcall {
 	const uint32_t *pred;   /* gate word of the pending call before */
 	uint32_t *gate;         /* this call's gate word (chained) or NULL */
 	struct sgpu_plan_in in; /* single stream: the plan input */
-	size_t foff;            /* ... fold area in w->pl */
+	size_t foff;            /* ... fold area in w->pl (fused: which w->fz
+				   slot is the call's) */
 	uint32_t nup;           /* many sessions: states uploaded */
 	uint64_t pend, done;    /* async: sequence numbers (mpg) */
 	double t[3];
@@ -365,9 +432,11 @@ struct dcall {
 	uint32_t spin;          /* synchronous: the post's completion word
 				   value to wait for (0: the stream) */
 	int radix;              /* ... grouped by the radix sort */
-	int fused;              /* single stream planned inside the crypto
-				   launch (fz_issue / fz_finish), 2: by the
-				   one-launch planner (lp_issue / lp_finish) */
+	int sync;               /* a synchronous call (dev_call), not a ticket */
+	int fused;              /* single stream, 1: planned inside the crypto
+				   launch, 2: by the one-launch planner in
+				   front of the lean kernel (fz_issue /
+				   fz_finish), 0: the separate planner */
 	struct sgpu_fused fz;   /* ... its launch */
 	int bucket;             /* many sessions: the bucket planner */
 	struct sgpu_bplan bp;   /* ... its launches */

@@ -148,16 +148,57 @@ def test_device_fold_across_batches(suite, torch_cuda):
     check(torch_cuda, suite, key, [b1, b2, b3], "batches")
 
 
-@pytest.mark.parametrize("suite", [1])
-def test_host_fold_knob_same_results(suite, torch_cuda):
-    """RE_SRTP_NODEVFOLD (srtp_gpu_tune nodevfold): the host engine folds
-    the same batches to the same results"""
+def host_fold_knob(torch, suite, **knobs):
+    """2 000 packets across the ROC wrap, three forged, nodevfold: the
+    call is undone on the device and folded on the host ("folds" moves
+    twice per such call: the device path counts the fold it hands over
+    and the host engine counts the one it runs)"""
     rng = np.random.default_rng(99)
     key = keys_for(suite, 1)[0]
     ob = O.OracleBackend()
     seqs = list(range(65300, 67300))
     pkts = forge(protect(ob, suite, key, seqs, rng), [3, 236, 1999], rng)
-    f0 = P.counter("devfolds")
-    with P.tune(nodevfold=1):
-        check(torch_cuda, suite, key, [pkts], "nodevfold")
+    f0, h0 = P.counter("devfolds"), P.counter("folds")
+    with P.tune(nodevfold=1, **knobs):
+        check(torch, suite, key, [pkts], "nodevfold")
+    print("nodevfold", suite, knobs, "devfolds", P.counter("devfolds") - f0,
+          "folds", P.counter("folds") - h0)
     assert P.counter("devfolds") == f0
+    assert P.counter("folds") > h0
+
+
+@pytest.mark.parametrize("suite", [1, 4])
+def test_host_fold_knob_same_results(suite, torch_cuda):
+    """RE_SRTP_NODEVFOLD (srtp_gpu_tune nodevfold): the host engine folds
+    the same batches to the same results -- behind the plan inside the
+    crypto launch (suite 1) and behind the one-launch planner with the
+    general kernels' undo (suite 4, AES-GCM)"""
+    host_fold_knob(torch_cuda, suite)
+
+
+def test_host_fold_knob_one_launch_planner(torch_cuda):
+    """... and AES-CM behind the one-launch planner (srtp_gpu_tune lplan),
+    undone by the fused kernel's undo pass"""
+    host_fold_knob(torch_cuda, 1, lplan=1)
+
+
+@pytest.mark.parametrize("name", ["timeout", "rollover"])
+def test_unsettled_fold_one_launch_planner(name, torch_cuda):
+    """AES-CM behind the one-launch planner (srtp_gpu_tune lplan): a fold
+    the device cannot settle is undone and folded on the host, to the
+    oracle's per-packet results and final state"""
+    suite = 1
+    rng = np.random.default_rng(123 + suite)
+    key = keys_for(suite, 1)[0]
+    ob = O.OracleBackend()
+    seqs, bad, devfold = cases(rng)[name]
+    assert not devfold
+    pkts = forge(protect(ob, suite, key, seqs, rng), bad, rng)
+    f0, h0 = P.counter("devfolds"), P.counter("folds")
+    p0 = P.counter("lplans")
+    with P.tune(lplan=1):
+        check(torch_cuda, suite, key, [pkts], name)
+    print(name, "devfolds", P.counter("devfolds") - f0, "folds",
+          P.counter("folds") - h0, "lplans", P.counter("lplans") - p0)
+    assert P.counter("folds") > h0, name
+    assert P.counter("devfolds") == f0, name

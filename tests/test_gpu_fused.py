@@ -3,9 +3,9 @@ k_ctr_fused.h (parse, every check, the ROC prefix over 1024-packet
 workgroups), in its two forms:
 
   fused   the AES-CM default: the plan inside the crypto launch
-          (k_ctr_fused, host dev_fused);
-  lplan   the plan as a launch of its own (k_lp_plan, host lp_issue /
-          lp_finish) in front of the lean crypto kernel -- AES-GCM always,
+          (k_ctr_fused, host fz_issue / fz_finish, kind 1);
+  lplan   the plan as a launch of its own (k_lp_plan, the same host pair,
+          kind 2) in front of the lean crypto kernel -- AES-GCM always,
           AES-CM with srtp_gpu_tune lplan (k_ctr_fast_any);
   *_copy  either with the plan out brought back by a blit copy
           (srtp_gpu_tune nopost) instead of the k_plan_post launch.
