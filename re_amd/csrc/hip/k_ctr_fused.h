@@ -54,44 +54,6 @@ struct FShared {
 	uint32_t seq[FZ_BLOCK + 2];     /* seq of packets base-2 .. base+B-1 */
 };
 
-/* SPF_* bits a look-back word carries (bits 32..45) */
-#define FZ_FMASK 0x3fffu
-static_assert((SPF_SLOW | SPF_SEG | SPF_PRED | 0x1ffu) <= FZ_FMASK, "fz_word");
-
-__device__ __forceinline__ uint64_t fz_word(uint32_t epoch, uint32_t st,
-					    uint32_t fail, uint32_t wraps)
-{
-	return (uint64_t)epoch << 48 | (uint64_t)st << 46 |
-	       (uint64_t)(fail & FZ_FMASK) << 32 | wraps;
-}
-
-__device__ __forceinline__ void fz_store(unsigned long long *w, uint64_t v)
-{
-	__hip_atomic_store(w, (unsigned long long)v, __ATOMIC_RELAXED,
-			   __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint64_t fz_load(unsigned long long *w)
-{
-	return __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1)
-		v += (uint32_t)__shfl_xor((int)v, o);
-	return v;
-}
-
-__device__ __forceinline__ uint32_t wave_or(uint32_t v)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1)
-		v |= (uint32_t)__shfl_xor((int)v, o);
-	return v;
-}
-
 #ifdef FZ_WTIME
 #define FZ_WTIME_MAX 4096u
 #define FZ_WREC 24u
@@ -205,28 +167,15 @@ __device__ __forceinline__ int fz_plan(const FArgs &fa, FShared &S,
 	if (live) {
 		sb = i == 0 ? s_l0 : S.seq[tid + 1];
 		const uint32_t L = e - p;
-		if (h.hdr_len == 0xffffffffu || hl0 == 0xffffffffu)
-			f |= SPF_PARSE;
-		else if (((h.hdr_len ^ hl0) >> 2) & 3u)
-			f |= SPF_CLASS;
-		/* (an unparsable packet has no SSRC: SPF_PARSE alone, so the
-		 * host does not try the per-stream planner for it) */
-		if (h.ssrc != ssrc0 && h.hdr_len != 0xffffffffu)
-			f |= SPF_SSRC;
-		if (!PROT && h.hdr_len != 0xffffffffu && L - h.hdr_len < in.tag)
-			f |= SPF_PARSE;
-		if (!PROT && (int)seq - (int)sb > 32768)
-			f |= SPF_TIMEOUT;
-		if (L >= in.maxlen)
-			f |= SPF_SIZE;
-		if ((p & 3u) || p > e || e > asz ||
-		    (P.cap && (e > cp || cp > asz)))
-			f |= SPF_BAD;
-		if (PROT && P.cap && (uint64_t)e + in.need > (uint64_t)cp)
-			f |= SPF_CAP;
-		wrap = plan_wrap(seq, sb);
-		if (i + 1 < n && !wrap && seq < sb)
-			f |= SPF_ORDER;
+		/* an unparsable packet has no SSRC: SPF_PARSE alone, so the
+		 * host does not try the per-stream planner for it */
+		f |= plan_header_flags(h.hdr_len, hl0, h.ssrc, ssrc0,
+				       PLAN_SSRC_PARSED, L, in.tag, 1, PROT);
+		f |= plan_window_flags(p, e, P.cap != NULL, cp, asz, in.maxlen,
+				       in.need, PROT);
+		const struct plan_ord o = plan_order(seq, sb, i + 1 >= n, PROT);
+		f |= o.flags;
+		wrap = o.wrap;
 		if (i == 0) {
 			P.out->ssrc0 = h.ssrc;
 			P.out->hl0 = h.hdr_len;
@@ -245,61 +194,12 @@ __device__ __forceinline__ int fz_plan(const FArgs &fa, FShared &S,
 	if (wv == 0) {
 		/* step 3: aggregate, look-back, inclusive prefix */
 		const uint32_t tot = wave_sum(lane < B / 64u ? S.wsum[lane] : 0u);
-		const uint32_t lf = S.fail;
-		uint32_t excl = 0, xf = 0;
-		if (t != 0) {
-			if (lane == 0)
-				fz_store(&P.agg[t], fz_word(P.epoch, 1, lf, tot));
-			int32_t j = (int32_t)t - 1;
-			for (;;) {
-				const int32_t k = j - (int32_t)lane;
-				uint64_t w = 0;
-				uint32_t st = 2;
-				if (k >= 0) {
-					/* every workgroup below t is running or
-					 * done and publishes before it waits; the
-					 * bound (2^18 polls of s_sleep 1, ~64
-					 * clocks each: ~7 ms at 2.4 GHz) only
-					 * turns a stalled predecessor or a broken
-					 * ticket count into a rejected plan
-					 * (SPF_SLOW: the host re-plans, resets
-					 * the counters and counts it apart from
-					 * a bad window, "lbtimeouts") instead of
-					 * a wave that never ends */
-					for (uint32_t spin = 0;; spin++) {
-						w = fz_load(&P.agg[k]);
-						st = (uint32_t)(w >> 46) & 3u;
-						if ((uint32_t)(w >> 48) == P.epoch &&
-						    st != 0)
-							break;
-						if (spin > (1u << 18)) {
-							w = fz_word(0, 2, SPF_SLOW, 0);
-							st = 2;
-							break;
-						}
-						__builtin_amdgcn_s_sleep(1);
-					}
-				}
-				const uint64_t inc = __ballot(st == 2);
-				const uint32_t first = inc ?
-					(uint32_t)__ffsll((long long)inc) - 1u : 64u;
-				const bool take = lane <= first;
-				excl += wave_sum(take ? (uint32_t)w : 0u);
-				xf |= wave_or(take ? (uint32_t)(w >> 32) & FZ_FMASK
-						   : 0u);
-				if (inc)
-					break;
-				j -= 64;
-			}
-		}
+		const struct fz_prefix pf = fz_lookback(P.agg, P.epoch, t, lane,
+							S.fail, tot,
+							&P.out->fail);
 		if (lane == 0) {
-			fz_store(&P.agg[t], fz_word(P.epoch, 2, lf | xf,
-						    excl + tot));
-			S.excl = excl;
-			S.xfail = lf | xf;
-			if (lf | (xf & (SPF_BAD | SPF_SLOW)))
-				atomicOr(&P.out->fail,
-					 lf | (xf & (SPF_BAD | SPF_SLOW)));
+			S.excl = pf.excl;
+			S.xfail = pf.fail;
 		}
 	}
 	__syncthreads();
@@ -316,43 +216,28 @@ __device__ __forceinline__ int fz_plan(const FArgs &fa, FShared &S,
 	for (uint32_t q = 0; q < wv; q++)
 		pre += S.wsum[q];
 	const uint32_t roc = in.roc + S.excl + pre + (wrap ? 1u : 0u);
-	uint64_t ix;
-	uint32_t fl = SD_RUN | SD_CIPHER;
-	if (PROT) {
-		ix = 65536ull * roc + seq;                      /* srtp.c:215 */
-	}
-	else {
-		const int32_t v = plan_v(roc, wrap ? 0u : sb, seq);
-		ix = seq + (uint64_t)(int64_t)v * 65536ull;
-		if ((uint32_t)v != roc)
-			fl |= (uint32_t)v + 1u == roc ? SD_ROC_P1 : SD_ROC_M1;
+	const struct plan_idx x = plan_index(roc, wrap, sb, seq, PROT);
+	const uint64_t ix = x.ix;
+	if (!PROT) {
 		bool ok;
 		if (i == 0) {
-			if (ix > in.lix)
-				ok = true;
-			else {
-				const uint64_t d = in.lix - ix;
-				ok = d < 64 && !(in.bitmap & (1ull << d));
-			}
+			ok = plan_new_first(ix, in.lix, in.bitmap);
 		}
 		else {
-			const uint32_t pseq = sb;       /* packet i-1's seq */
+			/* packet i-1: seq sb, seen from psb */
 			const uint32_t psb = i == 1 ? s_l0 : S.seq[tid];
-			const bool pw = plan_wrap(pseq, psb);
-			const uint32_t proc = roc - (wrap ? 1u : 0u);
-			const int32_t pv = plan_v(proc, pw ? 0u : psb, pseq);
-			const uint64_t pix = pseq + (uint64_t)(int64_t)pv * 65536ull;
-			ok = ix > pix && ix > in.lix;
+			ok = plan_new_later(ix, plan_prev_index(roc, wrap, psb, sb),
+					    in.lix);
 		}
 		if (!ok)
 			atomicOr(&P.out->fail, (uint32_t)SPF_REPLAY);
 	}
-	P.desc[i] = d_desc(ix, fl);
+	P.desc[i] = d_desc(ix, x.fl);
 	const uint32_t t0 = n > SGPU_PLAN_TAIL ? n - SGPU_PLAN_TAIL : 0u;
 	if (i >= t0)
 		P.out->tail_ix[i - t0] = ix;
 	if (i + 1 == n) {
-		P.out->s_l_last = wrap ? seq : (seq > sb ? seq : sb);
+		P.out->s_l_last = plan_s_l_after(seq, sb, wrap);
 		P.out->wraps = roc - in.roc;
 	}
 	/* k_plan_finish's results */
@@ -426,8 +311,8 @@ k_ctr_fused(const FArgs fa)
 /*
  * The plan alone, as its own launch in front of the lean crypto kernels
  * (k_ctr_fast_any, guarded by skip[] and out->fail; k_gcmu, guarded by
- * out->fail): the one-launch single-stream planner (batch_dev.c lp_issue).
- * It writes what k_parse, k_plan_count / scan / desc / final and
+ * out->fail): the one-launch single-stream planner (batch_dev.c fz_issue,
+ * path 2).  It writes what k_parse, k_plan_count / scan / desc / final and
  * k_plan_finish wrote (hdr, es, desc, the plan out, the results of every
  * packet planned) in one launch instead of six, and leaves the crypto
  * launch its full LDS and registers (the in-launch plan of k_ctr_fused
@@ -567,27 +452,15 @@ k_lp_plan(const FArgs fa)
 			const uint32_t sb = i == 0 ? s_l0 : S.seq[q + 1];
 			const uint32_t L = e - p;
 			sbv[j] = sb;
-			if (h.hdr_len == 0xffffffffu || hl0 == 0xffffffffu)
-				f |= SPF_PARSE;
-			else if (((h.hdr_len ^ hl0) >> 2) & 3u)
-				f |= SPF_CLASS;
-			if (h.ssrc != ssrc0 && h.hdr_len != 0xffffffffu)
-				f |= SPF_SSRC;
-			if (!PROT && h.hdr_len != 0xffffffffu &&
-			    L - h.hdr_len < in.tag)
-				f |= SPF_PARSE;
-			if (!PROT && (int)seq - (int)sb > 32768)
-				f |= SPF_TIMEOUT;
-			if (L >= in.maxlen)
-				f |= SPF_SIZE;
-			if ((p & 3u) || p > e || e > asz ||
-			    (P.cap && (e > cp || cp > asz)))
-				f |= SPF_BAD;
-			if (PROT && P.cap && (uint64_t)e + in.need > (uint64_t)cp)
-				f |= SPF_CAP;
-			wrap = plan_wrap(seq, sb);
-			if (i + 1 < n && !wrap && seq < sb)
-				f |= SPF_ORDER;
+			f |= plan_header_flags(h.hdr_len, hl0, h.ssrc, ssrc0,
+					       PLAN_SSRC_PARSED, L, in.tag, 1,
+					       PROT);
+			f |= plan_window_flags(p, e, P.cap != NULL, cp, asz,
+					       in.maxlen, in.need, PROT);
+			const struct plan_ord o = plan_order(seq, sb, i + 1 >= n,
+							     PROT);
+			f |= o.flags;
+			wrap = o.wrap;
 			if (i == 0) {
 				P.out->ssrc0 = h.ssrc;
 				P.out->hl0 = h.hdr_len;
@@ -609,51 +482,12 @@ k_lp_plan(const FArgs fa)
 #pragma unroll
 		for (int j = 0; j < LP_PPT; j++)
 			tot += wave_sum(lane < FZ_BLOCK / 64u ? S.wsum[j][lane] : 0u);
-		const uint32_t lf = S.fail;
-		uint32_t excl = 0, xf = 0;
-		if (t != 0) {
-			if (lane == 0)
-				fz_store(&P.agg[t], fz_word(P.epoch, 1, lf, tot));
-			int32_t jj = (int32_t)t - 1;
-			for (;;) {
-				const int32_t k = jj - (int32_t)lane;
-				uint64_t w = 0;
-				uint32_t st = 2;
-				if (k >= 0) {
-					for (uint32_t spin = 0;; spin++) {
-						w = fz_load(&P.agg[k]);
-						st = (uint32_t)(w >> 46) & 3u;
-						if ((uint32_t)(w >> 48) == P.epoch &&
-						    st != 0)
-							break;
-						if (spin > (1u << 18)) {
-							w = fz_word(0, 2, SPF_SLOW, 0);
-							st = 2;
-							break;
-						}
-						__builtin_amdgcn_s_sleep(1);
-					}
-				}
-				const uint64_t inc = __ballot(st == 2);
-				const uint32_t first = inc ?
-					(uint32_t)__ffsll((long long)inc) - 1u : 64u;
-				const bool take = lane <= first;
-				excl += wave_sum(take ? (uint32_t)w : 0u);
-				xf |= wave_or(take ? (uint32_t)(w >> 32) & FZ_FMASK
-						   : 0u);
-				if (inc)
-					break;
-				jj -= 64;
-			}
-		}
+		const struct fz_prefix pf = fz_lookback(P.agg, P.epoch, t, lane,
+							S.fail, tot,
+							&P.out->fail);
 		if (lane == 0) {
-			fz_store(&P.agg[t], fz_word(P.epoch, 2, lf | xf,
-						    excl + tot));
-			S.excl = excl;
-			S.xfail = lf | xf;
-			if (lf | (xf & (SPF_BAD | SPF_SLOW)))
-				atomicOr(&P.out->fail,
-					 lf | (xf & (SPF_BAD | SPF_SLOW)));
+			S.excl = pf.excl;
+			S.xfail = pf.fail;
 		}
 	}
 	__syncthreads();
@@ -674,47 +508,36 @@ k_lp_plan(const FArgs fa)
 			P.desc[i] = 0;          /* not planned */
 			continue;
 		}
-		/* fz_plan step 4: k_plan_desc (srtp_kernels.hip) */
+		/* fz_plan step 4: k_plan_desc (srtp_kernels.hip).  In place here
+		 * as there, on plan_rule.h's functions: one function for the two
+		 * sites shifted this kernel's register allocation (unprotect
+		 * build, 55 -> 54 VGPRs), which a refactor must not */
 		const uint32_t seq = hv[j].seq, sb = sbv[j];
 		const bool wrap = (wm[j] >> lane) & 1ull;
 		const uint32_t roc = in.roc + rpre + (wrap ? 1u : 0u);
-		uint64_t ix;
-		uint32_t fl = SD_RUN | SD_CIPHER;
-		if (PROT) {
-			ix = 65536ull * roc + seq;                      /* srtp.c:215 */
-		}
-		else {
-			const int32_t v = plan_v(roc, wrap ? 0u : sb, seq);
-			ix = seq + (uint64_t)(int64_t)v * 65536ull;
-			if ((uint32_t)v != roc)
-				fl |= (uint32_t)v + 1u == roc ? SD_ROC_P1 : SD_ROC_M1;
+		const struct plan_idx x = plan_index(roc, wrap, sb, seq, PROT);
+		const uint64_t ix = x.ix;
+		if (!PROT) {
 			bool ok;
 			if (i == 0) {
-				if (ix > in.lix)
-					ok = true;
-				else {
-					const uint64_t d = in.lix - ix;
-					ok = d < 64 && !(in.bitmap & (1ull << d));
-				}
+				ok = plan_new_first(ix, in.lix, in.bitmap);
 			}
 			else {
-				const uint32_t pseq = sb;       /* packet i-1's seq */
+				/* packet i-1: seq sb, seen from psb */
 				const uint32_t psb = i == 1 ? s_l0 : S.seq[q];
-				const bool pw = plan_wrap(pseq, psb);
-				const uint32_t proc = roc - (wrap ? 1u : 0u);
-				const int32_t pv2 = plan_v(proc, pw ? 0u : psb, pseq);
-				const uint64_t pix = pseq + (uint64_t)(int64_t)pv2 * 65536ull;
-				ok = ix > pix && ix > in.lix;
+				ok = plan_new_later(ix, plan_prev_index(roc, wrap,
+									psb, sb),
+						    in.lix);
 			}
 			if (!ok)
 				atomicOr(&P.out->fail, (uint32_t)SPF_REPLAY);
 		}
-		P.desc[i] = d_desc(ix, fl);
+		P.desc[i] = d_desc(ix, x.fl);
 		const uint32_t t0 = n > SGPU_PLAN_TAIL ? n - SGPU_PLAN_TAIL : 0u;
 		if (i >= t0)
 			P.out->tail_ix[i - t0] = ix;
 		if (i + 1 == n) {
-			P.out->s_l_last = wrap ? seq : (seq > sb ? seq : sb);
+			P.out->s_l_last = plan_s_l_after(seq, sb, wrap);
 			P.out->wraps = roc - in.roc;
 		}
 		/* k_plan_finish's results (the host puts the ends back if the

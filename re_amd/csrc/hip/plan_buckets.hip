@@ -249,25 +249,15 @@ k_bp_scatter(const uint8_t *__restrict__ arena, uint64_t asz,
 						 ((h.hdr_len >> 2) & 3u) != q;
 		}
 		/* the window checks of k_mp_count (via k_parse_rtp_checked) */
-		if (h.hdr_len == 0xffffffffu)
-			f |= SPF_PARSE;
-		else if (!P.prot && e - p - h.hdr_len < P.tag)
-			f |= SPF_PARSE;
-		if (e - p >= P.maxlen)
-			f |= SPF_SIZE;
-		if ((p & 3u) || p > e || e > asz ||
-		    (P.capv && (e > c || c > asz)))
-			f |= SPF_BAD;
-		if (P.prot && P.capv && (uint64_t)e + P.need > (uint64_t)c)
-			f |= SPF_CAP;
+		f |= plan_window_flags(p, e, P.capv != NULL, c, asz, P.maxlen,
+				       P.need, P.prot);
 		if (s >= P.nsess) {
 			f |= SPF_BAD;
 			s = P.nsess - 1u;
 		}
-		if (hl0 == 0xffffffffu)
-			f |= SPF_PARSE;
-		else if (h.hdr_len != 0xffffffffu && ((h.hdr_len ^ hl0) >> 2) & 3u)
-			f |= SPF_CLASS;
+		/* the SSRC is the plan kernel's, per session and order-free */
+		f |= plan_header_flags(h.hdr_len, hl0, 0, 0, PLAN_SSRC_NONE, e - p,
+				       P.tag, 1, P.prot);
 		/* the crypto launch order's class: descending 64-B chunks */
 		const uint32_t L = e >= p ? e - p : 0u, ch = (L + 63u) >> 6;
 		const uint32_t bin = (BP_OBINS - 1u) -
@@ -358,17 +348,9 @@ __device__ __forceinline__ uint64_t bp_ix(const BpPlanLds &S, uint32_t prot,
 	const bool wrap = plan_wrap(seq, sb);
 	/* ROC after this packet's own rollover */
 	const uint32_t roc = S.rbase[l] + S.pw[k];
-	uint64_t ix;
-	uint32_t fl = SD_RUN | SD_CIPHER;
-	if (prot) {
-		ix = 65536ull * roc + seq;                   /* srtp.c:215 */
-	}
-	else {
-		const int32_t v = plan_v(roc, wrap ? 0u : sb, seq);
-		ix = seq + (uint64_t)(int64_t)v * 65536ull;
-		if ((uint32_t)v != roc)
-			fl |= (uint32_t)v + 1u == roc ? SD_ROC_P1 : SD_ROC_M1;
-	}
+	const struct plan_idx x = plan_index(roc, wrap, sb, seq, prot);
+	const uint64_t ix = x.ix;
+	const uint32_t fl = x.fl;
 	if (flp)
 		*flp = fl;
 	if (rocp)
@@ -580,35 +562,23 @@ k_bp_plan(const struct sgpu_bplan P)
 			bool wrap;
 			const uint64_t ix = bp_ix(S, P.prot, k, f0, l, &fl, &roc,
 						  &wrap, &sb);
-			if (!P.prot && (int)seq - (int)sb > 32768)
-				f |= SPF_TIMEOUT;
-			if (!last && !wrap && seq < sb)
-				f |= SPF_ORDER;
+			f |= plan_order(seq, sb, last, P.prot).flags;
 			if (!P.prot) {
 				/* replay: every packet new (replay.c:32-62),
 				 * above the session's pre-batch lix as well */
 				const struct sgpu_sstate &x = S.st[l];
-				bool ok;
-				if (k == f0) {
-					if (ix > x.lix) {
-						ok = true;
-					}
-					else {
-						const uint64_t d = x.lix - ix;
-						ok = d < 64 && !(x.bitmap & (1ull << d));
-					}
-				}
-				else {
-					ok = ix > bp_ix(S, 0, k - 1, f0, l, NULL, NULL,
-							NULL, NULL) && ix > x.lix;
-				}
+				const bool ok = k == f0 ?
+					plan_new_first(ix, x.lix, x.bitmap) :
+					plan_new_later(ix, bp_ix(S, 0, k - 1, f0, l,
+								 NULL, NULL, NULL,
+								 NULL), x.lix);
 				if (!ok)
 					f |= SPF_REPLAY;
 			}
 			if (last) {
 				/* the session after the batch (k_mp_final) */
 				S.froc[l] = roc;
-				S.fsl[l] = wrap ? seq : (seq > sb ? seq : sb);
+				S.fsl[l] = plan_s_l_after(seq, sb, wrap);
 				S.lixl[l] = ix;
 			}
 			P.desc[i] = d_desc(ix, fl);
@@ -884,34 +854,21 @@ k_bp_finish(const struct sgpu_bplan P)
 			int32_t j = (int32_t)l;
 			while (j >= (int32_t)f0 && !S.au[j])
 				j--;
-			uint64_t lix = x.lix, bm = x.bitmap;
+			struct plan_win w = {x.lix, x.bitmap};
 			if (j >= (int32_t)f0) {
 				uint32_t q = f0;
 				if ((uint32_t)j - f0 >= 64u) {
 					q = (uint32_t)j - 63u;
-					const uint64_t d = P.desc[S.idx[q - 1]];
-					lix = (d & 0xffffull) |
-					      ((d >> 16) & 0xffffffffull) << 16;
-					bm = 0;
+					w.lix = d_desc_ix(P.desc[S.idx[q - 1]]);
+					w.bitmap = 0;
 				}
-				for (; q <= (uint32_t)j; q++) {
-					if (!S.au[q])
-						continue;
-					const uint64_t d = P.desc[S.idx[q]];
-					const uint64_t ix = (d & 0xffffull) |
-						((d >> 16) & 0xffffffffull) << 16;
-					if (ix > lix) {
-						const uint64_t dl = ix - lix;
-						bm = dl < 64 ? (bm << dl) | 1ull : 1ull;
-						lix = ix;
-					}
-					else {
-						bm |= 1ull << (lix - ix);
-					}
-				}
+				for (; q <= (uint32_t)j; q++)
+					if (S.au[q])
+						w = plan_win_step(w, d_desc_ix(
+							P.desc[S.idx[q]]));
 			}
-			o.lix = lix;
-			o.bitmap = bm;
+			o.lix = w.lix;
+			o.bitmap = w.bitmap;
 			bp_st(P.sout + s, o);
 		}
 		if (cf)

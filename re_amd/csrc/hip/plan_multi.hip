@@ -25,34 +25,13 @@
 #include <errno.h>
 #include <stdio.h>
 #include "../srtpgpu.h"
+#include "plan_common.h"
 
 #ifndef EAUTH
 #define EAUTH 217               /* include/re_types.h:215-217 */
 #endif
 
 #define MP_BLOCK 256
-
-__device__ __forceinline__ uint64_t mp_desc(uint64_t ix, uint32_t flags)
-{
-	return (ix & 0xffffull) | ((uint64_t)(uint32_t)(ix >> 16) << 16) |
-	       ((uint64_t)flags << 48);
-}
-
-/* misc.c:22-41, including the int wrap of roc +- 1 */
-__device__ __forceinline__ int32_t mp_v(uint32_t roc, uint32_t s_l,
-					uint32_t seq)
-{
-	if (s_l < 32768)
-		return ((int)seq - (int)s_l > 32768) ? (int32_t)(roc - 1)
-						     : (int32_t)roc;
-	return ((int)s_l - 32768 > (int)seq) ? (int32_t)(roc + 1)
-					     : (int32_t)roc;
-}
-
-__device__ __forceinline__ bool mp_wrap(uint32_t seq, uint32_t sb)
-{
-	return (int)seq - (int)sb <= -32768;
-}
 
 struct mp_ctx {
 	const uint32_t *key;            /* sorted session index */
@@ -272,34 +251,26 @@ k_mp_count(const struct sgpu_mplan_in in, mp_ctx c, const uint32_t *pos,
 					  : pseq;
 		if (s >= in.nsess)
 			f |= SPF_BAD;
-		if (h.hdr_len == 0xffffffffu || hl0 == 0xffffffffu)
-			f |= SPF_PARSE;
-		else if (((h.hdr_len ^ hl0) >> 2) & 3u)
-			f |= SPF_CLASS;
-		/* one SSRC per session: the stored one, or the segment's */
-		if (first ? ((S.flags & SST_EXISTS) && h.ssrc != S.ssrc)
-			  : h.ssrc != pssrc)
-			f |= SPF_SSRC;
-		if (!in.prot && (int)seq - (int)sb > 32768)
-			f |= SPF_TIMEOUT;
-		/* the window checks: made by the parse prologue (coalesced,
-		 * in.wchk, folded in by k_mp_scan) or here (gathers) */
-		if (!in.wchk) {
-			if (!in.prot && h.hdr_len != 0xffffffffu &&
-			    end[i] - pos[i] - h.hdr_len < in.tag)
-				f |= SPF_PARSE;
-			if (end[i] - pos[i] >= in.maxlen)
-				f |= SPF_SIZE;
-			if ((pos[i] & 3u) || pos[i] > end[i] || end[i] > asz ||
-			    (cap && (end[i] > cap[i] || cap[i] > asz)))
-				f |= SPF_BAD;
-			if (in.prot && cap &&
-			    (uint64_t)end[i] + in.need > (uint64_t)cap[i])
-				f |= SPF_CAP;
-		}
-		wrap = mp_wrap(seq, sb);
-		if (!last && !wrap && seq < sb)
-			f |= SPF_ORDER;
+		/* one SSRC per session: the stored one (a new session has none
+		 * yet), or the segment's previous packet's.  The window checks,
+		 * the tag's room among them: made by the parse prologue
+		 * (coalesced, in.wchk, folded in by k_mp_scan) or here (gathers) */
+		const bool wchk = in.wchk != NULL;
+		uint32_t L = 0;
+		if (!wchk)
+			L = end[i] - pos[i];
+		f |= plan_header_flags(h.hdr_len, hl0, h.ssrc,
+				       first ? S.ssrc : pssrc,
+				       first && !(S.flags & SST_EXISTS) ?
+				       PLAN_SSRC_NONE : PLAN_SSRC_ALWAYS,
+				       L, in.tag, !wchk, in.prot);
+		const struct plan_ord o = plan_order(seq, sb, last, in.prot);
+		f |= o.flags;
+		wrap = o.wrap;
+		if (!wchk)
+			f |= plan_window_flags(pos[i], end[i], cap != NULL,
+					       cap ? cap[i] : 0u, asz, in.maxlen,
+					       in.need, in.prot);
 		if (k == 0)
 			out->hl0 = hl0;
 		if (f)
@@ -356,7 +327,7 @@ k_mp_mark(mp_ctx c, const uint32_t *bpre, uint32_t *pex, uint32_t *segf,
 		last = k + 1 == c.n || c.key[k + 1] != c.key[k];
 		/* the segment start is only needed for k == f */
 		const uint32_t sb = first ? mp_sb(c, k, k) : c.sseq[k - 1];
-		wrap = mp_wrap(c.sseq[k], sb);
+		wrap = plan_wrap(c.sseq[k], sb);
 	}
 	const uint64_t m = __ballot(wrap);
 	if (lane == 0)
@@ -385,23 +356,15 @@ __device__ __forceinline__ uint64_t mp_ix(const mp_ctx &c,
 	const struct sgpu_sstate &S = c.st[c.key[k]];
 	const uint32_t seq = c.sseq[k];
 	const uint32_t sb = mp_sb(c, k, f);
-	const bool wrap = mp_wrap(seq, sb);
+	const bool wrap = plan_wrap(seq, sb);
 	const uint32_t fseq = c.sseq[f];
-	const bool wf = mp_wrap(fseq, mp_sb(c, f, f));
+	const bool wf = plan_wrap(fseq, mp_sb(c, f, f));
 	/* ROC after this packet's own rollover */
 	const uint32_t roc = S.roc + (pex[k] + (wrap ? 1u : 0u)) -
 			     (pex[f] + (wf ? 1u : 0u)) + (wf ? 1u : 0u);
-	uint64_t ix;
-	uint32_t fl = SD_RUN | SD_CIPHER;
-	if (in.prot) {
-		ix = 65536ull * roc + seq;                   /* srtp.c:215 */
-	}
-	else {
-		const int32_t v = mp_v(roc, wrap ? 0u : sb, seq);
-		ix = seq + (uint64_t)(int64_t)v * 65536ull;
-		if ((uint32_t)v != roc)
-			fl |= (uint32_t)v + 1u == roc ? SD_ROC_P1 : SD_ROC_M1;
-	}
+	const struct plan_idx x = plan_index(roc, wrap, sb, seq, in.prot);
+	const uint64_t ix = x.ix;
+	const uint32_t fl = x.fl;
 	if (flp)
 		*flp = fl;
 	if (rocp)
@@ -425,26 +388,15 @@ k_mp_desc(const struct sgpu_mplan_in in, mp_ctx c, const uint32_t *pex,
 	const uint64_t ix = mp_ix(c, in, pex, k, f, &fl, NULL, NULL, NULL);
 	if (!in.prot) {
 		/* replay: every packet new (replay.c:32-62) */
-		bool ok;
-		if (k == f) {
-			const struct sgpu_sstate &S = c.st[s];
-			if (ix > S.lix)
-				ok = true;
-			else {
-				const uint64_t d = S.lix - ix;
-				ok = d < 64 && !(S.bitmap & (1ull << d));
-			}
-		}
-		else {
-			/* above the session's pre-batch lix as well (see
-			 * k_plan_desc, srtp_kernels.hip) */
-			ok = ix > mp_ix(c, in, pex, k - 1, f, NULL, NULL, NULL,
-					NULL) && ix > c.st[s].lix;
-		}
+		const struct sgpu_sstate &S = c.st[s];
+		const bool ok = k == f ?
+			plan_new_first(ix, S.lix, S.bitmap) :
+			plan_new_later(ix, mp_ix(c, in, pex, k - 1, f, NULL, NULL,
+						 NULL, NULL), S.lix);
 		if (!ok)
 			atomicOr(&out->fail, (uint32_t)SPF_REPLAY);
 	}
-	desc[c.val[k]] = mp_desc(ix, fl);
+	desc[c.val[k]] = d_desc(ix, fl);
 }
 
 /* final state of every touched session; launch guards */
@@ -475,33 +427,24 @@ k_mp_final(const struct sgpu_mplan_in in, mp_ctx c, const uint32_t *pex,
 	const uint32_t seq = c.sseq[l];
 	o.ssrc = (S.flags & SST_EXISTS) ? S.ssrc : c.sssrc[f];
 	o.roc = roc;
-	o.s_l = wrap ? seq : (seq > sb ? seq : sb);
+	o.s_l = plan_s_l_after(seq, sb, wrap);
 	o.flags = SST_EXISTS | SST_SL_SET | SST_TOUCHED;
 	if (!in.prot) {
 		/* replay fold over the last <= 65 indices (older bits have
 		 * shifted out: every index is new and increasing) */
-		uint64_t lix = S.lix, bm = S.bitmap;
+		struct plan_win w = {S.lix, S.bitmap};
 		uint32_t k = f;
 		if (l - f + 1 > 65) {
 			k = l - 64;
-			lix = mp_ix(c, in, pex, k - 1, f, NULL, NULL, NULL,
-				    NULL);
-			bm = 1;
+			w.lix = mp_ix(c, in, pex, k - 1, f, NULL, NULL, NULL,
+				      NULL);
+			w.bitmap = 1;
 		}
-		for (; k <= l; k++) {
-			const uint64_t ix = mp_ix(c, in, pex, k, f, NULL, NULL,
-						  NULL, NULL);
-			if (ix > lix) {
-				const uint64_t d = ix - lix;
-				bm = d < 64 ? (bm << d) | 1ull : 1ull;
-				lix = ix;
-			}
-			else {
-				bm |= 1ull << (lix - ix);
-			}
-		}
-		o.lix = lix;
-		o.bitmap = bm;
+		for (; k <= l; k++)
+			w = plan_win_step(w, mp_ix(c, in, pex, k, f, NULL, NULL,
+						   NULL, NULL));
+		o.lix = w.lix;
+		o.bitmap = w.bitmap;
 	}
 	st_out[s] = o;
 }
@@ -641,7 +584,7 @@ __device__ __forceinline__ uint32_t mf_sb(const mf_ctx &c, uint32_t k,
 __device__ __forceinline__ bool mf_event(const mf_ctx &c, uint32_t k)
 {
 	const uint32_t s = mf_key(c, k), f = c.segf[s];
-	return mf_auth(c, k) || mp_wrap(c.sseq[k], mf_sb(c, k, f, s));
+	return mf_auth(c, k) || plan_wrap(c.sseq[k], mf_sb(c, k, f, s));
 }
 
 /* true s_l after event position e (-1 or outside the segment: the
@@ -741,12 +684,12 @@ k_mf_check(mf_ctx c, const int32_t *bprev, struct sgpu_sstate *st_out,
 	const uint32_t seq = c.sseq[k];
 	const uint32_t sb = mf_sb(c, k, f, s);          /* speculated */
 	const uint32_t sl = mf_slv(c, e, f, s);         /* true */
-	const bool wrap = mp_wrap(seq, sb);
-	bool bad = mp_wrap(seq, sl) != wrap ||
+	const bool wrap = plan_wrap(seq, sb);
+	bool bad = plan_wrap(seq, sl) != wrap ||
 		   (int)seq - (int)sl > 32768;          /* ETIMEDOUT */
 	if (!bad && !wrap) {
 		/* same index estimate (misc.c:22-41) at any ROC */
-		bad = mp_v(65536u, sl, seq) != mp_v(65536u, sb, seq);
+		bad = plan_v(65536u, sl, seq) != plan_v(65536u, sb, seq);
 		/* an authentic packet sets s_l = seq only if seq > s_l
 		 * (srtp.c:426-427); the events assume it does */
 		if (mf_auth(c, k) && seq < sl)
@@ -794,33 +737,20 @@ k_mf_final(mf_ctx c, const uint32_t *segl, const uint64_t *desc,
 	int32_t j = (int32_t)l;
 	while (j >= (int32_t)f && !mf_auth(c, (uint32_t)j))
 		j--;
-	uint64_t lix = S.lix, bm = S.bitmap;
+	struct plan_win w = {S.lix, S.bitmap};
 	if (j >= (int32_t)f) {
 		uint32_t q = f;
 		if ((uint32_t)j - f >= 64u) {
 			q = (uint32_t)j - 63u;
-			const uint64_t d = desc[c.val[q - 1]];
-			lix = (d & 0xffffull) | ((d >> 16) & 0xffffffffull) << 16;
-			bm = 0;
+			w.lix = d_desc_ix(desc[c.val[q - 1]]);
+			w.bitmap = 0;
 		}
-		for (; q <= (uint32_t)j; q++) {
-			if (!mf_auth(c, q))
-				continue;
-			const uint64_t d = desc[c.val[q]];
-			const uint64_t ix = (d & 0xffffull) |
-					    ((d >> 16) & 0xffffffffull) << 16;
-			if (ix > lix) {
-				const uint64_t dl = ix - lix;
-				bm = dl < 64 ? (bm << dl) | 1ull : 1ull;
-				lix = ix;
-			}
-			else {
-				bm |= 1ull << (lix - ix);
-			}
-		}
+		for (; q <= (uint32_t)j; q++)
+			if (mf_auth(c, q))
+				w = plan_win_step(w, d_desc_ix(desc[c.val[q]]));
 	}
-	st_out[s].lix = lix;
-	st_out[s].bitmap = bm;
+	st_out[s].lix = w.lix;
+	st_out[s].bitmap = w.bitmap;
 }
 
 /* ---- host side ------------------------------------------------------ */

@@ -37,6 +37,7 @@
 #include <errno.h>
 #include <stdio.h>
 #include "../srtpgpu.h"
+#include "plan_common.h"
 
 #define SP_BLOCK 1024
 #define SP_WAVES (SP_BLOCK / 64)
@@ -51,29 +52,6 @@
 #define SP_BL_SSRC(bl, nb, j, b)  (bl)[(size_t)(j) * (nb) + (b)]
 #define SP_BL_FIRST(bl, nb, j, b) (bl)[(size_t)(SP_H + (j)) * (nb) + (b)]
 #define SP_BL_LAST(bl, nb, j, b)  (bl)[(size_t)(2 * SP_H + (j)) * (nb) + (b)]
-
-__device__ __forceinline__ uint64_t sp_desc(uint64_t ix, uint32_t flags)
-{
-	return (ix & 0xffffull) | ((uint64_t)(uint32_t)(ix >> 16) << 16) |
-	       ((uint64_t)flags << 48);
-}
-
-/* srtp_get_index (misc.c:22-41), including the int wrap of roc +- 1 */
-__device__ __forceinline__ int32_t sp_v(uint32_t roc, uint32_t s_l,
-					uint32_t seq)
-{
-	if (s_l < 32768)
-		return ((int)seq - (int)s_l > 32768) ? (int32_t)(roc - 1)
-						     : (int32_t)roc;
-	return ((int)s_l - 32768 > (int)seq) ? (int32_t)(roc + 1)
-					     : (int32_t)roc;
-}
-
-/* ROC rollover seen by a packet (srtp.c:208-213, 318-321) */
-__device__ __forceinline__ bool sp_wrap(uint32_t seq, uint32_t sb)
-{
-	return (int)seq - (int)sb <= -32768;
-}
 
 __device__ __forceinline__ int32_t sp_top(uint64_t m)
 {
@@ -441,19 +419,15 @@ k_sp_count(const struct sgpu_splan_in in, const struct sgpu_hdr *hdr,
 		const uint32_t seq = h.seq;
 		const uint32_t sb = p >= 0 ? (uint32_t)hdr[p].seq : sp_sb0(L, k, seq);
 		const uint32_t hl0 = hdr[0].hdr_len;
-		if (hl0 == 0xffffffffu)
-			f |= SPF_PARSE;
-		else if (((h.hdr_len ^ hl0) >> 2) & 3u)
-			f |= SPF_CLASS;
-		if (!in.prot && end[i] - pos[i] - h.hdr_len < in.tag)
-			f |= SPF_PARSE;
-		if (!in.prot && (int)seq - (int)sb > 32768)
-			f |= SPF_TIMEOUT;
-		wrap = sp_wrap(seq, sb);
-		/* the next packet of the stream sees s_l = seq only if this one
-		 * left it so */
-		if ((int32_t)i != L.last[k] && !wrap && seq < sb)
-			f |= SPF_ORDER;
+		/* no SSRC check here: the packet's SSRC chose its stream k */
+		f |= plan_header_flags(h.hdr_len, hl0, 0, 0, PLAN_SSRC_NONE,
+				       end[i] - pos[i], in.tag, 1, in.prot);
+		/* (last: the stream's last packet of the batch) */
+		const struct plan_ord o = plan_order(seq, sb,
+						     (int32_t)i == L.last[k],
+						     in.prot);
+		f |= o.flags;
+		wrap = o.wrap;
 		rec[i] = sb | (wrap ? 1u << 16 : 0u) | k << 17;
 		prv[i] = p;
 	}
@@ -462,14 +436,9 @@ k_sp_count(const struct sgpu_splan_in in, const struct sgpu_hdr *hdr,
 		prv[i] = -1;
 	}
 	if (i < in.n) {
-		if (end[i] - pos[i] >= in.maxlen)
-			f |= SPF_SIZE;
-		if ((pos[i] & 3u) || pos[i] > end[i] || end[i] > asz ||
-		    (cap && (end[i] > cap[i] || cap[i] > asz)))
-			f |= SPF_BAD;
-		if (in.prot && cap &&
-		    (uint64_t)end[i] + in.need > (uint64_t)cap[i])
-			f |= SPF_CAP;
+		f |= plan_window_flags(pos[i], end[i], cap != NULL,
+				       cap ? cap[i] : 0u, asz, in.maxlen, in.need,
+				       in.prot);
 		if (i == 0)
 			out->base.hl0 = h.hdr_len;
 		if (f)
@@ -583,51 +552,33 @@ k_sp_desc(const struct sgpu_splan_in in, const struct sgpu_hdr *hdr,
 	const uint32_t seq = hdr[i].seq;
 	/* ROC after this packet's own rollover */
 	const uint32_t roc = (known ? S.roc : 0u) + wb + (wrap ? 1u : 0u);
-	uint64_t ix;
-	uint32_t fl = SD_RUN | SD_CIPHER;
-	if (in.prot) {
-		ix = 65536ull * roc + seq;              /* srtp.c:215 */
-	}
-	else {
-		const int32_t v = sp_v(roc, wrap ? 0u : sb, seq);
-		ix = seq + (uint64_t)(int64_t)v * 65536ull;
-		if ((uint32_t)v != roc)
-			fl |= (uint32_t)v + 1u == roc ? SD_ROC_P1 : SD_ROC_M1;
+	const struct plan_idx x = plan_index(roc, wrap, sb, seq, in.prot);
+	const uint64_t ix = x.ix;
+	if (!in.prot) {
 		const uint64_t lix = known ? S.lix : 0ull;
 		const uint64_t bm = known ? S.bitmap : 0ull;
 		/* replay: every packet of the stream new (replay.c:32-62) */
 		const int32_t p = prv[i];
 		bool ok;
 		if (p < 0) {
-			if (ix > lix) {
-				ok = true;
-			}
-			else {
-				const uint64_t d = lix - ix;
-				ok = d < 64 && !(bm & (1ull << d));
-			}
+			ok = plan_new_first(ix, lix, bm);
 		}
 		else {
 			const uint32_t pr = rec[p];
-			const uint32_t psb = pr & 0xffffu;
-			const bool pw = (pr >> 16) & 1u;
-			const uint32_t pseq = hdr[p].seq;
-			const uint32_t proc = roc - (wrap ? 1u : 0u);
-			const int32_t pv = sp_v(proc, pw ? 0u : psb, pseq);
-			const uint64_t pix = pseq + (uint64_t)(int64_t)pv * 65536ull;
-			/* above the pre-batch window too (see k_plan_desc) */
-			ok = ix > pix && ix > lix;
+			ok = plan_new_later(ix, plan_prev_index(roc, wrap,
+								pr & 0xffffu,
+								hdr[p].seq), lix);
 		}
 		if (!ok)
 			atomicOr(&out->base.fail, (uint32_t)SPF_REPLAY);
 	}
-	desc[i] = sp_desc(ix, fl);
+	desc[i] = d_desc(ix, x.fl);
 	const uint32_t C = cnt[k];
 	const uint32_t t0 = C > SGPU_PLAN_TAIL ? C - SGPU_PLAN_TAIL : 0u;
 	if (ord >= t0 && ord - t0 < SGPU_PLAN_TAIL)
 		out->tail_ix[k][ord - t0] = ix;
 	if ((int32_t)i == L.last[k])
-		out->s_l_last[k] = wrap ? seq : (seq > sb ? seq : sb);
+		out->s_l_last[k] = plan_s_l_after(seq, sb, wrap);
 }
 
 __global__ void k_sp_final(struct sgpu_splan_out *out)

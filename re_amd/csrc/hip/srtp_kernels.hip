@@ -421,29 +421,18 @@ k_plan_count(const struct sgpu_plan_in in, const struct sgpu_hdr *hdr,
 		const uint32_t hl0 = hdr[0].hdr_len;
 		const uint32_t ssrc0 = in.ssrc_any ? hdr[0].ssrc : in.ssrc;
 		const uint32_t seq = h.seq, sb = plan_sb(in, hdr, i);
-		if (h.hdr_len == 0xffffffffu || hl0 == 0xffffffffu)
-			f |= SPF_PARSE;
-		else if (((h.hdr_len ^ hl0) >> 2) & 3u)
-			f |= SPF_CLASS;
-		if (h.ssrc != ssrc0)
-			f |= SPF_SSRC;
-		if (!in.prot && h.hdr_len != 0xffffffffu &&
-		    end[i] - pos[i] - h.hdr_len < in.tag)
-			f |= SPF_PARSE;
-		if (!in.prot && (int)seq - (int)sb > 32768)
-			f |= SPF_TIMEOUT;
-		if (end[i] - pos[i] >= in.maxlen)
-			f |= SPF_SIZE;
-		if ((pos[i] & 3u) || pos[i] > end[i] || end[i] > asz ||
-		    (cap && (end[i] > cap[i] || cap[i] > asz)))
-			f |= SPF_BAD;
-		if (in.prot && cap &&
-		    (uint64_t)end[i] + in.need > (uint64_t)cap[i])
-			f |= SPF_CAP;
-		wrap = plan_wrap(seq, sb);
-		/* the next packet sees s_l = seq only if this one left it so */
-		if (i + 1 < in.n && !wrap && seq < sb)
-			f |= SPF_ORDER;
+		/* the SSRC whatever the parse left (0 for an unparsable header),
+		 * unlike the one-launch planners: SPF_SSRC with SPF_PARSE */
+		f |= plan_header_flags(h.hdr_len, hl0, h.ssrc, ssrc0,
+				       PLAN_SSRC_ALWAYS, end[i] - pos[i], in.tag,
+				       1, in.prot);
+		f |= plan_window_flags(pos[i], end[i], cap != NULL,
+				       cap ? cap[i] : 0u, asz, in.maxlen, in.need,
+				       in.prot);
+		const struct plan_ord o = plan_order(seq, sb, i + 1 >= in.n,
+						     in.prot);
+		f |= o.flags;
+		wrap = o.wrap;
 		if (i == 0) {
 			out->ssrc0 = h.ssrc;
 			out->hl0 = h.hdr_len;
@@ -509,49 +498,25 @@ k_plan_desc(const struct sgpu_plan_in in, const struct sgpu_hdr *hdr,
 		return;
 	/* ROC after this packet's own rollover */
 	const uint32_t roc = in.roc + bpre[blockIdx.x] + pre + (wrap ? 1u : 0u);
-	uint64_t ix;
-	uint32_t fl = SD_RUN | SD_CIPHER;
-	if (in.prot) {
-		ix = 65536ull * roc + seq;              /* srtp.c:215 */
-	}
-	else {
-		const int32_t v = plan_v(roc, wrap ? 0u : sb, seq);
-		ix = seq + (uint64_t)(int64_t)v * 65536ull;
-		if ((uint32_t)v != roc)
-			fl |= (uint32_t)v + 1u == roc ? SD_ROC_P1 : SD_ROC_M1;
+	const struct plan_idx x = plan_index(roc, wrap, sb, seq, in.prot);
+	const uint64_t ix = x.ix;
+	if (!in.prot) {
 		/* replay: every packet must be new (replay.c:32-62) */
-		bool ok;
-		if (i == 0) {
-			if (ix > in.lix)
-				ok = true;
-			else {
-				const uint64_t d = in.lix - ix;
-				ok = d < 64 && !(in.bitmap & (1ull << d));
-			}
-		}
-		else {
-			const uint32_t pseq = hdr[i - 1].seq;
-			const uint32_t psb = plan_sb(in, hdr, i - 1);
-			const bool pw = plan_wrap(pseq, psb);
-			const uint32_t proc = roc - (wrap ? 1u : 0u);
-			const int32_t pv = plan_v(proc, pw ? 0u : psb, pseq);
-			const uint64_t pix = pseq +
-					     (uint64_t)(int64_t)pv * 65536ull;
-			/* above the pre-batch window too: a packet 0 below
-			 * lix leaves the window's bits in play (replay.c:53-61)
-			 * and the tail-based final window (plan_replay) holds
-			 * only for indices above it */
-			ok = ix > pix && ix > in.lix;
-		}
+		const bool ok = i == 0 ?
+			plan_new_first(ix, in.lix, in.bitmap) :
+			plan_new_later(ix, plan_prev_index(roc, wrap,
+							   plan_sb(in, hdr, i - 1),
+							   hdr[i - 1].seq),
+				       in.lix);
 		if (!ok)
 			atomicOr(&out->fail, (uint32_t)SPF_REPLAY);
 	}
-	desc[i] = d_desc(ix, fl);
+	desc[i] = d_desc(ix, x.fl);
 	const uint32_t t0 = in.n > SGPU_PLAN_TAIL ? in.n - SGPU_PLAN_TAIL : 0u;
 	if (i >= t0)
 		out->tail_ix[i - t0] = ix;
 	if (i + 1 == in.n)
-		out->s_l_last = wrap ? seq : (seq > sb ? seq : sb);
+		out->s_l_last = plan_s_l_after(seq, sb, wrap);
 }
 
 /* ------------------------------------------------------------------ */
@@ -562,6 +527,24 @@ __device__ __forceinline__ uint32_t rplan_eix(const struct sgpu_rplan_in &in,
 {
 	/* the E || index word at end - 4 - tag (k_parse, tl = 0, 4, 10) */
 	return eix[3 * i + (in.tag == 0 ? 0 : in.tag == 4 ? 1 : 2)];
+}
+
+/* what both SRTCP planners write for packet i */
+__device__ __forceinline__ void rplan_emit(const struct plan_rtcp r, uint32_t i,
+					   uint32_t n, uint32_t ssrc,
+					   uint64_t *desc,
+					   struct sgpu_plan_out *out)
+{
+	desc[i] = plan_rtcp_desc(r.ix, r.E);
+	const uint32_t t0 = n > SGPU_PLAN_TAIL ? n - SGPU_PLAN_TAIL : 0u;
+	if (i >= t0)
+		out->tail_ix[i - t0] = r.ix;
+	if (i == 0) {
+		out->ssrc0 = ssrc;
+		out->hl0 = 8;
+	}
+	if (r.flags)
+		atomicOr(&out->fail, r.flags);
 }
 
 __global__ void __launch_bounds__(PLAN_BLOCK)
@@ -575,71 +558,16 @@ k_plan_rtcp(const struct sgpu_rplan_in in, const struct sgpu_hdr *hdr,
 		return;
 	const struct sgpu_hdr h = hdr[i];
 	const uint32_t ssrc0 = in.ssrc_any ? hdr[0].ssrc : in.ssrc;
-	const uint32_t L = end[i] - pos[i];
-	uint32_t f = 0;
-	if (h.hdr_len == 0xffffffffu)
-		f |= SPF_PARSE;                 /* < 8 bytes: EBADMSG */
-	else if (h.ssrc != ssrc0)
-		f |= SPF_SSRC;
-	if ((pos[i] & 3u) || pos[i] > end[i] || end[i] > asz ||
-	    (cap && (end[i] > cap[i] || cap[i] > asz)))
-		f |= SPF_BAD;
-	if (L >= in.maxlen)
-		f |= SPF_SIZE;
-	uint32_t ix, E;
-	if (in.prot) {
-		if (cap && (uint64_t)end[i] + in.need > (uint64_t)cap[i])
-			f |= SPF_CAP;           /* ENOMEM (cap_short) */
-		ix = (in.rtcp_index + i + 1u) & 0x7fffffffu;    /* srtcp.c:54 */
-		E = in.encrypted;
-	}
-	else {
-		/* srtcp.c:166-172 (and 239-241 for GCM): room for E || index,
-		 * the tag, and the GCM tag before them */
-		if (L < 8u + 4u + in.tag + (in.gcm ? 16u : 0u))
-			f |= SPF_PARSE;
-		const uint32_t v = rplan_eix(in, eix, i);
-		ix = v & 0x7fffffffu;
-		E = v >> 31;
-		if (in.hmac) {
-			/* replay (srtcp.c:208-209), speculated: every index new
-			 * and increasing */
-			bool ok;
-			if (i == 0) {
-				if (ix > in.lix) {
-					ok = true;
-				}
-				else {
-					const uint64_t dl = in.lix - ix;
-					ok = dl < 64 && !(in.bitmap & (1ull << dl));
-				}
-			}
-			else {
-				ok = ix > (rplan_eix(in, eix, i - 1) & 0x7fffffffu);
-			}
-			if (!ok)
-				f |= SPF_REPLAY;
-		}
-	}
-	desc[i] = ((uint64_t)(ix & 0x7fffffffu)) | ((uint64_t)E << 31) |
-		  ((uint64_t)SD_RUN << 48);
-	const uint32_t t0 = in.n > SGPU_PLAN_TAIL ? in.n - SGPU_PLAN_TAIL : 0u;
-	if (i >= t0)
-		out->tail_ix[i - t0] = ix;
-	if (i == 0) {
-		out->ssrc0 = h.ssrc;
-		out->hl0 = 8;
-	}
-	if (f)
-		atomicOr(&out->fail, f);
+	/* the header and the E || index words from k_parse's arrays */
+	const bool rx = !in.prot;
+	const struct plan_rtcp r = plan_rtcp_packet(
+		in, i, h.hdr_len != 0xffffffffu, h.ssrc, ssrc0, end[i] - pos[i],
+		plan_window_flags(pos[i], end[i], cap != NULL, cap ? cap[i] : 0u,
+				  asz, in.maxlen, in.need, in.prot),
+		rx ? rplan_eix(in, eix, i) : 0u,
+		rx && in.hmac && i > 0 ? rplan_eix(in, eix, i - 1) : 0u);
+	rplan_emit(r, i, in.n, h.ssrc, desc, out);
 }
-
-extern "C" int sgpu_plan_rtcp(const struct sgpu_rplan_in *in,
-			      const struct sgpu_hdr *hdr, const uint32_t *eix,
-			      const uint32_t *pos, const uint32_t *end,
-			      const uint32_t *cap, uint64_t arena_size,
-			      uint64_t *desc, struct sgpu_plan_out *out,
-			      void *stream);
 
 /* the E || index word of SRTCP packet i (k_parse's eix word for the
  * stream's tag length) */
@@ -710,62 +638,15 @@ k_rp_plan(const uint8_t *__restrict__ arena, uint64_t asz,
 	if (!live)
 		return;
 	const uint32_t ssrc0 = in.ssrc_any ? ssrc0s : in.ssrc;
-	const uint32_t L = e - p;
-	uint32_t f = 0;
-	if (h.hdr_len == 0xffffffffu)
-		f |= SPF_PARSE;                 /* < 8 bytes: EBADMSG */
-	else if (h.ssrc != ssrc0)
-		f |= SPF_SSRC;
-	if ((p & 3u) || p > e || e > asz || (R.cap && (e > c || c > asz)))
-		f |= SPF_BAD;
-	if (L >= in.maxlen)
-		f |= SPF_SIZE;
-	uint32_t ix, E;
-	if (in.prot) {
-		if (R.cap && (uint64_t)e + in.need > (uint64_t)c)
-			f |= SPF_CAP;           /* ENOMEM (cap_short) */
-		ix = (in.rtcp_index + i + 1u) & 0x7fffffffu;    /* srtcp.c:54 */
-		E = in.encrypted;
-	}
-	else {
-		/* srtcp.c:166-172 (and 239-241 for GCM) */
-		if (L < 8u + 4u + in.tag + (in.gcm ? 16u : 0u))
-			f |= SPF_PARSE;
-		ix = v & 0x7fffffffu;
-		E = v >> 31;
-		if (in.hmac) {
-			/* replay (srtcp.c:208-209), speculated: every index new
-			 * and increasing */
-			bool ok;
-			if (i == 0) {
-				if (ix > in.lix) {
-					ok = true;
-				}
-				else {
-					const uint64_t dl = in.lix - ix;
-					ok = dl < 64 && !(in.bitmap & (1ull << dl));
-				}
-			}
-			else {
-				ok = ix > (vw[tid] & 0x7fffffffu);
-			}
-			if (!ok)
-				f |= SPF_REPLAY;
-		}
-	}
-	R.desc[i] = ((uint64_t)(ix & 0x7fffffffu)) | ((uint64_t)E << 31) |
-		    ((uint64_t)SD_RUN << 48);
-	const uint32_t t0 = in.n > SGPU_PLAN_TAIL ? in.n - SGPU_PLAN_TAIL : 0u;
-	if (i >= t0)
-		R.out->tail_ix[i - t0] = ix;
-	if (i == 0) {
-		R.out->ssrc0 = h.ssrc;
-		R.out->hl0 = 8;
-	}
-	/* (no results here: the workgroup after this one reads this
-	 * packet's end for its replay order) */
-	if (f)
-		atomicOr(&R.out->fail, f);
+	/* the header and the word from this launch's own parse, the word
+	 * before it through LDS.  (No results here: the workgroup after this
+	 * one reads this packet's end for its replay order.) */
+	const struct plan_rtcp r = plan_rtcp_packet(
+		in, i, h.hdr_len != 0xffffffffu, h.ssrc, ssrc0, e - p,
+		plan_window_flags(p, e, R.cap != NULL, c, asz, in.maxlen, in.need,
+				  in.prot),
+		v, vw[tid]);
+	rplan_emit(r, i, in.n, h.ssrc, R.desc, R.out);
 }
 
 /* ================================================================== */
