@@ -284,9 +284,9 @@ int srtp_alloc_many(struct srtp **srtpv, size_t n, enum srtp_suite suite,
  * planner launches, not the plan inside the crypto launch), "fzepoch"
  * (test hook, process-wide and one-shot: the next fused launch of any
  * thread takes this look-back epoch, its look-back words zeroed first),
- * "norxplan" (a one-stream unprotect batch whose device plan was rejected
- * for reordered or replayed packets goes straight to the host engine, not
- * to the device receive planner),
+ * "norxplan" (an unprotect batch, one stream or many sessions, whose device
+ * plan was rejected for reordered or replayed packets goes straight to the
+ * host engine, not to the device receive planner),
  * "rxseq" (srtp_rx_index* and srtp_rx_fold walk
  * in one sequential pass, not in parallel parts), "freshmulti" (the
  * planner's first-batch hint: 1 sends a session's first batch to the
@@ -311,8 +311,10 @@ int srtp_gpu_tune(const char *name, long value);
  * the host completed, re-run when waited for), "freshmulti" (the
  * first-batch hint, 0/1), "rxplans" (reordered / duplicated one-stream
  * unprotect batches completed by the device receive planner), "rxlate"
- * (late packets it accepted), "rxdups" (EALREADY verdicts it gave).  0 for
- * an unknown name.
+ * (late packets it accepted), "rxdups" (EALREADY verdicts it gave),
+ * "mrxplans" (reordered / duplicated many-session unprotect batches
+ * completed by the bucket receive planner; "rxlate" and "rxdups" count its
+ * packets too).  0 for an unknown name.
  */
 uint64_t srtp_gpu_counter(const char *name);
 

@@ -83,6 +83,53 @@ RX_FN struct rx_agg rx_combine(struct rx_agg a, struct rx_agg b)
 	return r;
 }
 
+/*
+ * Many streams in one scan (plan_buckets_rx.hip: the packets of a bucket
+ * sorted by session): an element carries a segment-head flag beside its
+ * pair.  A head on the right operand restarts the sum and the maximum, so
+ * the inclusive scan of position k holds its own stream's pair only and
+ * u[] / Mx[] restart at each stream's first packet (a head's element: its
+ * u[0] itself, as packet 0's above).
+ */
+struct rx_seg {
+	struct rx_agg a;
+	uint32_t head;          /* a stream's first packet lies in the range */
+};
+
+RX_FN struct rx_seg rx_seg_identity(void)
+{
+	struct rx_seg r;
+	r.a = rx_identity();
+	r.head = 0;
+	return r;
+}
+
+RX_FN struct rx_seg rx_seg_elem(int64_t d, int head)
+{
+	struct rx_seg r;
+	r.a = rx_elem(d);
+	r.head = head ? 1u : 0u;
+	return r;
+}
+
+/* a then b: associative; rx_seg_identity() on either side */
+RX_FN struct rx_seg rx_seg_combine(struct rx_seg a, struct rx_seg b)
+{
+	struct rx_seg r;
+	if (b.head)
+		return b;
+	r.a = rx_combine(a.a, b.a);
+	r.head = a.head;
+	return r;
+}
+
+/* the exclusive prefix maximum of a position from the scan's exclusive
+ * value before it: nothing for a stream's first packet */
+RX_FN int64_t rx_seg_mx(struct rx_seg excl, int head)
+{
+	return head ? RX_NEG : excl.a.m;
+}
+
 /* seq - prev as the nearest signed distance, in (-32768, 32768] */
 RX_FN int64_t rx_sdiff16(uint32_t seq, uint32_t prev)
 {

@@ -81,6 +81,13 @@ static void tk_finish_one(void)
 		r = run_dev(k->op, k->sessv, k->nsess, &k->d);
 	}
 	else if (r == -1) {
+		/* reordered or replayed arrivals inside some session: the bucket
+		 * receive planner, before the states are read back */
+		if (t->kind == TK_MPLANNED && k->bucket &&
+		    mrx_eligible(k->op, k->nsess, k->pfail))
+			r = dev_mrxplanned(k->sessv, k->nsess, &k->d);
+	}
+	if (r == -1) {
 		r = sess_host(k->sessv, k->nsess);
 		/* a second SSRC in a single-stream plan: the per-stream one */
 		if (!r && t->kind == TK_PLANNED && (k->pfail & SPF_SSRC))
@@ -366,7 +373,12 @@ static int run_dev(int op, struct srtp **sessv, size_t nsess,
 	/* many sessions: planned on the device against the resident states */
 	if ((op == OP_RTP_ENC || op == OP_RTP_DEC) && nsess > 1 && d->sess &&
 	    !g_env.noplan && !g_env.general) {
-		int r = dev_mplanned(op, sessv, nsess, d);
+		uint32_t pf = 0;
+		int r = dev_mplanned(op, sessv, nsess, d, &pf);
+		/* reordered or replayed arrivals inside some session: the bucket
+		 * receive planner, the states staying resident */
+		if (r == -1 && mrx_eligible(op, nsess, pf))
+			r = dev_mrxplanned(sessv, nsess, d);
 		if (r >= 0)
 			return r;
 	}

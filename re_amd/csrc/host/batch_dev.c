@@ -6,8 +6,8 @@
  * one stream by the separate planner kernels (dp_issue / dp_finish;
  * dev_planned picks among the three), reordered arrivals (plan_rx.hip),
  * several streams of one session (plan_streams.hip), SRTCP
- * (dev_planned_rtcp) and many sessions with resident state
- * (dev_mplanned).  Each call is a struct dcall between its launches
+ * (dev_planned_rtcp), many sessions with resident state (dev_mplanned) and
+ * their reordered arrivals (plan_buckets_rx.hip, dev_mrxplanned).  Each call is a struct dcall between its launches
  * (*_issue) and its completion (*_finish), so the synchronous calls
  * (dev_call) and the asynchronous tickets (batch_async.c) share it.  Where a
  * call's arrays lie in the workspace pools: struct ws_layout (srtp_int.h)
@@ -1791,11 +1791,215 @@ int dev_mplanned_(int op, struct srtp **sessv, size_t nsess,
 /* a session with more than SGPU_MP_SEGMAX packets (SPF_SEG): re-planned
  * with the radix-sort grouping */
 int dev_mplanned(int op, struct srtp **sessv, size_t nsess,
-			struct srtp_batch_dev *d)
+			struct srtp_batch_dev *d, uint32_t *pfail)
 {
 	uint32_t pf = 0;
 	int r = dev_mplanned_(op, sessv, nsess, d, g_env.mpradix, &pf);
 	if (r == -1 && (pf & SPF_SEG) && !g_env.mpradix)
 		r = dev_mplanned_(op, sessv, nsess, d, 1, &pf);
+	*pfail = pf;
 	return r;
+}
+
+/* ---- many sessions, reordered / duplicated arrivals -------------------- */
+
+/* a rejected many-session unprotect plan the bucket receive planner
+ * (plan_buckets_rx.hip) may settle: the bucket planner produced it, and only
+ * the arrival order or a replayed index inside some session was in its way
+ * (a batch the buckets do not take: dev_mrxplanned's -1) */
+int mrx_eligible(int op, size_t nsess, uint32_t pfail)
+{
+	return op == OP_RTP_DEC && nsess > 1 && !g_env.norxplan &&
+	       !g_env.nobucket && !g_env.mpradix && pfail &&
+	       !(pfail & ~(uint32_t)(SPF_ORDER | SPF_REPLAY));
+}
+
+/*
+ * A many-session unprotect batch behind such a rejection, every array in
+ * HBM, against the resident states: the bucket scatter again (the rejected
+ * plan's finish zeroed its counters), the state gather of
+ * dev_bplanned_issue, sgpu_bplan_rx_plan, the general descriptor-driven
+ * crypto launches in array order guarded by its verdict, sgpu_bplan_rx_finish
+ * (results and the commit of the touched states, only if every packet was
+ * settled and every tag verified), one synchronisation.
+ * 0: done, the states advanced on the device (the sessions stay resident,
+ * as after dev_mplanned); -1: not settled, a batch the gather refuses, or a
+ * forged packet (undone) -- nothing modified, the caller's fallback
+ * continues; errno.
+ *
+ * w->bp as dev_bplanned_issue lays it out, with the per-bucket counts and
+ * the verdict bytes in place of the launch order; w->pl: plan out | fold out
+ * (unused) | sgpu_bprx_out.
+ */
+int dev_mrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
+{
+	const struct comp *c0 = &sessv[0]->rtp;
+	const size_t n = d->n;
+	const int gcm = c0->mode == SGPU_MODE_GCM;
+	const uint32_t T = gcm ? 16u : c0->tag_len;
+	const size_t na = (n + SGPU_BP_BLOCK * SGPU_BP_PPT - 1) /
+			  (SGPU_BP_BLOCK * SGPU_BP_PPT);
+	const size_t roff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
+		.vs = n * 5 + 64, .cm = nsess * 4, .pl = roff + 128, .es = n * 4};
+	struct ws_layout L;
+	struct sgpu_bplan_rx R;
+	struct sgpu_bplan *B = &R.b;
+	struct sgpu_compact C;
+	struct sgpu_plan_out *po, *po_d;
+	const struct sgpu_bprx_out *ro;
+	struct sgpu_sstate *up_h, *up_d;
+	uint8_t *need_h, *need_d, *p;
+	uint32_t *cm_h, bshift, nb, cap, nup = 0;
+	void *stream = d->stream;
+	struct ws *w;
+	int err;
+
+	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
+		return -1;
+	w = ws_get();
+	if (!w)
+		return ENOMEM;
+	err = ws_layout_reserve(w, n, &z, &L);
+	if (!err)   /* uploads | need */
+		err = pool_reserve(w, &w->ms,
+				   nsess * (sizeof(struct sgpu_sstate) + 1));
+	if (!err)
+		err = pool_reserve(w, &w->bp, BP_HEAD +
+				   sgpu_bplan_scratch((uint32_t)n, (uint32_t)nsess,
+						      nb, cap) +
+				   (size_t)nb * 8 + n + 512);
+	if (err)
+		return err;
+	if (w->bp_d != w->bp.d) {
+		/* a new pool (or a call that did not finish): counters from
+		 * zero */
+		err = sgpu_memset(w->bp.d, 0, BP_HEAD, stream);
+		if (err)
+			return err;
+		w->bp_d = w->bp.d;
+	}
+	po = (struct sgpu_plan_out *)w->pl.h;
+	po_d = (struct sgpu_plan_out *)w->pl.d;
+	ro = (const struct sgpu_bprx_out *)(w->pl.h + roff + 64);
+	memset(&R, 0, sizeof(R));
+	B->n = (uint32_t)n;
+	B->nsess = (uint32_t)nsess;
+	B->tag = T;
+	B->maxlen = SGPU_CACHED_MAX(c0->mode);
+	B->bshift = bshift;
+	B->nb = nb;
+	B->cap = cap;
+	B->delta = -(int32_t)T;
+	B->gcm = (uint32_t)gcm;
+	B->pos = d->pos;
+	B->end = d->end;
+	B->capv = d->cap;
+	B->sess = d->sess;
+	B->posw = d->pos;
+	B->endw = d->end;
+	B->err = d->err;
+	B->es = L.es;
+	B->hdr = L.hdr;
+	B->desc = L.desc;
+	p = w->bp.d;
+	B->ticket = (uint32_t *)p;
+	B->obins = (uint32_t *)(p + 64);
+	B->bcount = (uint32_t *)(p + 512);
+	p += BP_HEAD;
+#define BP_TAKE(ptr, bytes)                                                  \
+	do {                                                                 \
+		(ptr) = (void *)p;                                           \
+		p += ((size_t)(bytes) + 255) & ~(size_t)255;                 \
+	} while (0)
+	BP_TAKE(B->tmp, (size_t)nb * cap * 16);
+	BP_TAKE(B->sorted, (size_t)nb * cap * 4);
+	BP_TAKE(B->afail, na * 4);
+	BP_TAKE(B->sseg, nsess * 4);
+	BP_TAKE(B->sout, nsess * sizeof(struct sgpu_sstate));
+	BP_TAKE(R.cnt, (size_t)nb * 8);
+	BP_TAKE(R.rs, n);
+#undef BP_TAKE
+	B->sst = sgpu_sst_table();
+	B->out = po_d;
+	/* (the scatter zeroes fo->fail; nothing else uses the fold out) */
+	B->fo = (struct sgpu_fold_out *)(w->pl.d + roff);
+	R.ro = (struct sgpu_bprx_out *)(w->pl.d + roff + 64);
+	B->nfail = L.nfail;
+	B->verdict = L.verdict;
+	R.lookback = RX_LOOKBACK;
+	R.hmac = !gcm;
+	err = sgpu_bplan_scatter(d->arena, d->arena_size, B, stream);
+	if (err) {
+		w->bp_d = NULL;
+		return err;
+	}
+	cm_h = (uint32_t *)w->cm.h;
+	up_h = (struct sgpu_sstate *)w->ms.h;
+	need_h = (uint8_t *)(up_h + nsess);
+	up_d = (struct sgpu_sstate *)w->ms.d;
+	need_d = (uint8_t *)(up_d + nsess);
+	if (mplan_gather_res(sessv, nsess, up_h, cm_h, need_h, &nup, 0, 0)) {
+		/* the scatter only wrote scratch -- and the bucket counters,
+		 * zeroed again before the workspace's next call */
+		w->bp_d = NULL;
+		err = sgpu_stream_sync(stream);
+		return err ? err : -1;
+	}
+	/* the slot map (and any state the device lacks: none behind a bucket
+	 * plan that just uploaded them) on the call's stream */
+	err = sgpu_memcpy_h2d(w->cm.d, cm_h, nsess * 4, stream);
+	if (!err && nup)
+		err = sgpu_memcpy_h2d(up_d, up_h,
+				      nsess * (sizeof(struct sgpu_sstate) + 1),
+				      stream);
+	B->cm = (const uint32_t *)w->cm.d;
+	B->upneed = nup ? need_d : NULL;
+	B->up = up_d;
+	if (!err)
+		err = sgpu_bplan_rx_plan(&R, stream);
+	/* the general kernels (EALREADY packets: MAC only) with per-packet
+	 * session keys, array order: AES-CM picks the header class from
+	 * skip[], GCM has one */
+	C = compact_of(d, &L);
+	C.sess = d->sess;
+	C.guard = gcm ? &po_d->fail : po_d->skip;
+	if (!err)
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, gcm ? 0 : -1, 0, stream);
+	B->outbytes = (uint32_t)(roff + 64 + sizeof(struct sgpu_bprx_out));
+	B->outh = g_env.nopost ? NULL : (uint32_t *)w->pl.h;
+	if (!err)
+		err = sgpu_bplan_rx_finish(&R, stream);
+	if (!err && g_env.nopost)
+		err = sgpu_memcpy_d2h(w->pl.h, w->pl.d, B->outbytes, stream);
+	if (!err)
+		err = sgpu_stream_sync(stream);
+	if (err) {
+		sgpu_stream_sync(stream);       /* no copy still reads cm_h */
+		w->bp_d = NULL;
+		return err;
+	}
+	if (po->fail) {
+		if (g_env.times)
+			fprintf(stderr, "re_srtp mrx plan n=%zu nsess=%zu: not "
+				"settled (SPF %#x)\n", n, nsess, po->fail);
+		return -1;
+	}
+	if (po->nfail) {
+		/* a forged packet: undo on the device (no result and no state
+		 * was written), fold on the host engine */
+		count(&g_cnt_misses, po->nfail);
+		count(&g_cnt_folds, 1);
+		C.undo = 1;
+		err = run_classes(d->arena, d->arena_size, C, c0, po_d, 0, stream);
+		if (!err)
+			err = sgpu_stream_sync(stream);
+		return err ? err : -1;
+	}
+	count(&g_cnt_mrxplans, 1);
+	count(&g_cnt_rxlate, ro->nlate);
+	count(&g_cnt_rxdups, ro->ndup);
+	return 0;
 }

@@ -134,6 +134,10 @@ uint64_t g_cnt_rxplans;  /* reordered / duplicated one-stream unprotect
 				   (plan_rx.hip) */
 uint64_t g_cnt_rxlate;   /* ... late packets it accepted */
 uint64_t g_cnt_rxdups;   /* ... EALREADY verdicts it gave */
+uint64_t g_cnt_mrxplans; /* reordered / duplicated many-session unprotect
+				   batches completed by the bucket receive
+				   planner (plan_buckets_rx.hip); rxlate and
+				   rxdups count its packets too */
 uint64_t g_cnt_lbtimeout; /* fused launches rejected by a look-back
 				   wait past its bound (SPF_SLOW) */
 /* a session's first batch (no stream yet) goes to the per-stream planner
@@ -192,6 +196,8 @@ uint64_t srtp_gpu_counter(const char *name)
 		return __atomic_load_n(&g_cnt_lplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "rxplans"))
 		return __atomic_load_n(&g_cnt_rxplans, __ATOMIC_RELAXED);
+	if (!strcmp(name, "mrxplans"))
+		return __atomic_load_n(&g_cnt_mrxplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "rxlate"))
 		return __atomic_load_n(&g_cnt_rxlate, __ATOMIC_RELAXED);
 	if (!strcmp(name, "rxdups"))

@@ -121,11 +121,12 @@ struct srtp_env {
 				   (default 1000) */
 	int rxseq;              /* srtp_gpu_tune rxseq: srtp_rx_index* and
 				   srtp_rx_fold walk sequentially (A/B) */
-	int norxplan;           /* srtp_gpu_tune norxplan: a one-stream
-				   unprotect plan rejected for reordered or
-				   replayed packets goes straight to the host
-				   engine, not to the receive planner
-				   (plan_rx.hip) */
+	int norxplan;           /* srtp_gpu_tune norxplan: an unprotect plan
+				   rejected for reordered or replayed packets
+				   goes straight to the host engine, not to
+				   the receive planner (one stream:
+				   plan_rx.hip; many sessions:
+				   plan_buckets_rx.hip) */
 	int smallsync;          /* srtp_gpu_tune smallsync: wait for a small
 				   launch by a stream synchronisation, not
 				   its completion word */
@@ -284,7 +285,7 @@ extern uint64_t g_cnt_misses, g_cnt_folds, g_cnt_rejects, g_cnt_devfolds;
 extern uint64_t g_cnt_splans, g_cnt_fused, g_cnt_gated;
 extern uint64_t g_cnt_dplans, g_cnt_mplans, g_cnt_rplans, g_cnt_lbtimeout;
 extern uint64_t g_cnt_lplans;
-extern uint64_t g_cnt_rxplans, g_cnt_rxlate, g_cnt_rxdups;
+extern uint64_t g_cnt_rxplans, g_cnt_rxlate, g_cnt_rxdups, g_cnt_mrxplans;
 extern int g_fresh_multi;       /* srtp.c: the last first batch of a session
 				   showed several SSRCs (see there) */
 extern __thread struct tk_owner *t_own; /* srtp.c: this thread's async
@@ -498,7 +499,10 @@ int dev_mplanned_finish(struct dcall *k);
 int dev_mplanned_(int op, struct srtp **sessv, size_t nsess,
 			 struct srtp_batch_dev *d, int radix, uint32_t *pfail);
 int dev_mplanned(int op, struct srtp **sessv, size_t nsess,
-			struct srtp_batch_dev *d);
+			struct srtp_batch_dev *d, uint32_t *pfail);
+int mrx_eligible(int op, size_t nsess, uint32_t pfail);
+int dev_mrxplanned(struct srtp **sessv, size_t nsess,
+		   struct srtp_batch_dev *d);
 
 /* batch_async.c */
 void tk_drain(void);

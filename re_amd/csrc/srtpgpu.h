@@ -702,6 +702,47 @@ int   sgpu_bplan_plan(const struct sgpu_bplan *b, void *stream);
 int   sgpu_bplan_finish(const struct sgpu_bplan *b, void *stream);
 
 /*
+ * The receive planner of a multi-session UNPROTECT batch (one stream per
+ * session) behind a bucket plan rejected with SPF_ORDER / SPF_REPLAY only
+ * (plan_buckets_rx.hip; the rule per session segment: hip/plan_rx_rule.h):
+ *   sgpu_bplan_scatter    again, unchanged (b: prot 0, pred / gate / flist
+ *                         NULL; it zeroes out->fail and *nfail and opens
+ *                         packet 0's class guard)
+ *   sgpu_bplan_rx_plan    per bucket: states (+ uploads), the grouping of
+ *                         sgpu_bplan_plan, the segmented scan, rx_settle per
+ *                         packet with tags verified behind it; desc as
+ *                         sgpu_plan_rx writes it, rs[], sout[], cnt[]; an
+ *                         unsettled packet or a failed check: out->fail |=,
+ *                         out->skip[0..3] = 1
+ *   (the general crypto kernels over every packet in array order, guarded
+ *   by out->skip[] -- GCM: out->fail -- counting their tag misses in *nfail)
+ *   sgpu_bplan_rx_finish  if !out->fail and !*nfail: pos / end / err (0 or
+ *                         EALREADY), the touched states into the resident
+ *                         table; always: bcount / obins back to zero,
+ *                         out->nfail, *ro, and outbytes from out to outh
+ * out->fail or out->nfail after it: nothing of the caller's was modified
+ * but the packets the crypto launches processed (undo: the same kernels,
+ * sgpu_compact undo).  b->order, sorted, sseg, ticket, fo are not used.
+ */
+struct sgpu_bprx_out {
+	uint32_t nlate;         /* packets accepted below their window's top */
+	uint32_t ndup;          /* EALREADY verdicts */
+};
+
+struct sgpu_bplan_rx {
+	struct sgpu_bplan b;
+	uint8_t *rs;            /* [packet] verdict (RX_OK / RX_DUP) */
+	uint32_t *cnt;          /* nb x 2: late, duplicates per bucket */
+	struct sgpu_bprx_out *ro;       /* inside [out, out + outbytes) */
+	uint32_t lookback;      /* in-session arrivals searched for a
+				   duplicate's original (RX_LOOKBACK) */
+	uint32_t hmac;          /* HMAC suite: EALREADY packets are not
+				   decrypted */
+};
+int   sgpu_bplan_rx_plan(const struct sgpu_bplan_rx *r, void *stream);
+int   sgpu_bplan_rx_finish(const struct sgpu_bplan_rx *r, void *stream);
+
+/*
  * Device-side planning of a single-stream SRTCP batch (srtcp_encrypt
  * srtcp.c:31-140, srtcp_decrypt srtcp.c:143-287): protect numbers the
  * packets rtcp_index + 1, + 2, ...; unprotect reads E || index from each
