@@ -1181,3 +1181,36 @@ int oracle_stream_set(struct osrtp *s, uint32_t ssrc, uint32_t roc,
 	st->replay_rtp.bitmap = bitmap;
 	return 0;
 }
+
+/* SRTCP state of ssrc: the sender's index and the receiver's replay window
+ * (struct srtp_stream, src/srtp/srtp.h:29-38); -1 if no such stream */
+int oracle_rtcp_state(const struct osrtp *s, uint32_t ssrc,
+		      uint32_t *rtcp_index, uint64_t *lix, uint64_t *bitmap)
+{
+	int i;
+	for (i = 0; i < s->nstreams; i++) {
+		const struct ostream *st = &s->streams[i];
+		if (st->ssrc != ssrc)
+			continue;
+		*rtcp_index = st->rtcp_index;
+		*lix = st->replay_rtcp.lix;
+		*bitmap = st->replay_rtcp.bitmap;
+		return 0;
+	}
+	return -1;
+}
+
+/* test hook: set (or create) ssrc's SRTCP state -- a stream taken up near
+ * the 31-bit index wrap (tests/test_gpu_srtcp_replay.py) */
+int oracle_rtcp_set(struct osrtp *s, uint32_t ssrc, uint32_t rtcp_index,
+		    uint64_t lix, uint64_t bitmap)
+{
+	struct ostream *st;
+	int err = stream_get(&st, s, ssrc);
+	if (err)
+		return err;
+	st->rtcp_index = rtcp_index;
+	st->replay_rtcp.lix = lix;
+	st->replay_rtcp.bitmap = bitmap;
+	return 0;
+}

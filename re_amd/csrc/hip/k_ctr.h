@@ -76,6 +76,9 @@ __device__ __forceinline__ void ctr_hmac_body(const KArgs &a, uint8_t *smem)
 		prof_guard(a);
 	if (COMPACT && a.c.guard && *a.c.guard)  /* rejected plan / class */
 		return;
+	/* the bucket planner's fail word: its skip[] is packet 0's class alone */
+	if (COMPACT && a.c.gfail && *a.c.gfail)
+		return;
 	if (COMPACT || !a.nocipher)     /* MAC only: no AES */
 		tt4_fill(smem, a.t0);
 	__syncthreads();
@@ -562,6 +565,8 @@ k_ctr_hmac_any(const KArgs a)
 {
 	__shared__ __attribute__((aligned(16))) uint8_t smem[TT4_BYTES];
 	prof_guard(a);
+	if (a.c.gfail && *a.c.gfail)
+		return;                 /* the bucket planner's plan failed */
 	const uint32_t *g = a.c.guard;
 	const uint32_t q = !g[3] ? 3u : !g[0] ? 0u : !g[1] ? 1u : !g[2] ? 2u
 								    : 4u;
@@ -569,6 +574,7 @@ k_ctr_hmac_any(const KArgs a)
 		return;                 /* rejected plan */
 	KArgs b = a;
 	b.c.guard = NULL;
+	b.c.gfail = NULL;
 	switch (q) {
 	case 0: ctr_hmac_body<NR, 0, PROT, true, UNI>(b, smem); break;
 	case 1: ctr_hmac_body<NR, 1, PROT, true, UNI>(b, smem); break;

@@ -255,8 +255,11 @@ __device__ __forceinline__ void ctr_fast_pkt(const KArgs &a, uint8_t *smem,
 	const uint32_t T = PROT ? 0u : __builtin_amdgcn_readfirstlane(cp->tag_len);
 	/* MAC data / cipher end */
 	const uint32_t A = f.L - T - (RTCP && !PROT ? 4u : 0u);
-	/* unencrypted SRTCP (E = 0): an empty cipher region */
-	const uint32_t hl = RTCP && !(f.roc >> 31) ? A : f.hl;
+	/* unencrypted SRTCP (E = 0, or a receiver without a cipher:
+	 * srtcp.c:214 "rtcp->aes && ep"; the sender's plan sets E from its
+	 * own cipher): an empty cipher region */
+	const bool enc = !RTCP || ((f.roc >> 31) && (PROT || (cp->flags & 1u)));
+	const uint32_t hl = enc ? f.hl : A;
 
 	uint32_t iv[4];
 	fast_iv(cp, f, iv);
@@ -462,7 +465,9 @@ __device__ __forceinline__ void ctr_fast_pkt(const KArgs &a, uint8_t *smem,
 		uint32_t diff = 0;
 		for (uint32_t q = 0; q < tag_len; q++)
 			diff |= tp[q] ^ (uint8_t)(h[q >> 2] >> (24 - 8 * (q & 3)));
-		const uint8_t vd = (diff == 0 ? SV_TAG_OK : 0) | SV_CIPHERED;
+		/* nothing deciphered: nothing for an undo to restore */
+		const uint8_t vd = (diff == 0 ? SV_TAG_OK : 0) |
+				   (enc ? SV_CIPHERED : 0);
 		if (!(vd & SV_TAG_OK))
 			atomicAdd(a.c.nfail, 1u);
 		if (a.verdict)

@@ -252,11 +252,10 @@ PLAN_FN struct plan_rtcp plan_rtcp_packet(struct sgpu_rplan_in in, uint32_t i,
 	r.E = word >> 31;
 	if (in.hmac) {
 		/* replay (srtcp.c:208-209), speculated: every index new and
-		 * increasing.  The later-packet test lacks plan_new_later's
-		 * "above the pre-batch lix" (SRTCP replay
-		 * acceptance); kept as it is here, to be fixed on its own */
+		 * increasing, a later one above the pre-batch lix too */
 		const int ok = i == 0 ? plan_new_first(r.ix, in.lix, in.bitmap)
-				      : r.ix > (pword & 0x7fffffffu);
+				      : plan_new_later(r.ix, pword & 0x7fffffffu,
+						       in.lix);
 		if (!ok)
 			r.flags |= SPF_REPLAY;
 	}

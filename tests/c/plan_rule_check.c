@@ -483,10 +483,80 @@ static void check_rtcp(void)
 	ixv[0] = 70000 - 64;
 	CHECK(rtcp_batch(70000, bm, ixv, 66, &w) == SPF_REPLAY,
 	      "rtcp first below the window");
-	/* (left out: packet 0 below lix on a clear bit, packet 1 above it on a
-	 * set bit of the window.  The later-packet test has no "above the
-	 * pre-batch lix" yet and accepts it -- ADVICE.md, the SRTCP replay
-	 * acceptance item; the case belongs to that fix.) */
+	/* packet 0 below lix on a clear bit, packet 1 above it on a set bit of
+	 * the window: the receiver says EALREADY to packet 1 */
+	ixv[0] = 69941;                 /* bit 59: clear */
+	ixv[1] = 69945;                 /* bit 55: set */
+	for (i = 2; i < 66; i++)
+		ixv[i] = 70000 + i;
+	CHECK(rtcp_batch(70000, bm, ixv, 66, &w) == SPF_REPLAY,
+	      "rtcp late first, second on a set bit");
+	CHECK(rtcp_batch(70000, bm, ixv, 2, &w) == SPF_REPLAY,
+	      "rtcp late first, second on a set bit, n 2");
+}
+
+#define RTCP_RANDOM 200000u
+
+/* plan_rtcp_packet + plan_win_step against the sequential replay check, on
+ * short batches around the stored window: whatever the rule accepts, the
+ * receiver accepts packet by packet and leaves the same window.  The two
+ * shares at the end keep the generator honest: the rule must accept a good
+ * part of the batches, and the receiver must turn a packet down in a good
+ * part of them (a rule that accepted those would be caught). */
+static void check_rtcp_random(void)
+{
+	uint32_t ixv[6], b, i, k, accepted = 0, refused = 0;
+	for (b = 0; b < RTCP_RANDOM; b++) {
+		const uint32_t n = 1 + rnd() % 6;
+		uint64_t lix = 0, bitmap = 0;
+		struct plan_win w;
+		struct rx r;
+		uint32_t lo, down = 0;
+		if (b % 3) {
+			lix = b % 3 == 1 ? 40 + rnd() % 60 : 70000;
+			bitmap = ((uint64_t)rnd() << 40 ^ (uint64_t)rnd() << 20 ^
+				  rnd()) | 1;
+			/* no history below index 0 */
+			if (lix < 63)
+				bitmap &= (2ull << lix) - 1;
+		}
+		lo = lix > 70 ? (uint32_t)lix - 70 : 0;
+		for (i = 0; i < n; i++)
+			ixv[i] = lo + rnd() % ((uint32_t)lix + 70 - lo + 1);
+		if (rnd() & 3) {                /* three in four: ascending */
+			for (i = 1; i < n; i++) {
+				const uint32_t t = ixv[i];
+				for (k = i; k > 0 && ixv[k - 1] > t; k--)
+					ixv[k] = ixv[k - 1];
+				ixv[k] = t;
+			}
+		}
+		r.roc = 0;
+		r.s_l = 0;
+		r.lix = lix;
+		r.bitmap = bitmap;
+		for (i = 0; i < n; i++)
+			down += !ref_replay_check(&r, ixv[i]);
+		refused += down != 0;
+		if (rtcp_batch(lix, bitmap, ixv, n, &w))
+			continue;
+		accepted++;
+		CHECK(down == 0, "rtcp random: lix %llu bitmap %llx n %u (%u %u %u "
+		      "%u %u %u): the receiver turns %u down",
+		      (unsigned long long)lix, (unsigned long long)bitmap, n, ixv[0],
+		      n > 1 ? ixv[1] : 0, n > 2 ? ixv[2] : 0, n > 3 ? ixv[3] : 0,
+		      n > 4 ? ixv[4] : 0, n > 5 ? ixv[5] : 0, down);
+		CHECK(down || (r.lix == w.lix && r.bitmap == w.bitmap),
+		      "rtcp random: lix %llu n %u: window (%llx, %llx), not "
+		      "(%llx, %llx)", (unsigned long long)lix, n,
+		      (unsigned long long)w.lix, (unsigned long long)w.bitmap,
+		      (unsigned long long)r.lix, (unsigned long long)r.bitmap);
+	}
+	printf("rtcp random: %u of %u batches accepted, the receiver turns a "
+	       "packet down in %u\n", accepted, RTCP_RANDOM, refused);
+	CHECK(accepted >= RTCP_RANDOM * 3 / 10, "rtcp random: %u accepted",
+	      accepted);
+	CHECK(refused >= RTCP_RANDOM * 3 / 10, "rtcp random: %u refused", refused);
 }
 
 int main(void)
@@ -496,6 +566,7 @@ int main(void)
 	check_reject();
 	check_random();
 	check_rtcp();
+	check_rtcp_random();
 	printf("%d wrong\n", g_bad);
 	return g_bad ? 1 : 0;
 }

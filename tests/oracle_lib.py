@@ -60,6 +60,9 @@ def _load():
     lib.oracle_stream_set.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32,
                                       ctypes.c_uint32, ctypes.c_uint32,
                                       ctypes.c_uint64, ctypes.c_uint64]
+    lib.oracle_rtcp_state.argtypes = [vp, ctypes.c_uint32, u32p, u64p, u64p]
+    lib.oracle_rtcp_set.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32,
+                                    ctypes.c_uint64, ctypes.c_uint64]
     return lib
 
 
@@ -97,6 +100,18 @@ class OracleBackend:
                                       ctypes.byref(b)):
             return (0, 0, 0, 0)
         return (r.value, s.value, x.value, b.value)
+
+    def rtcp_state(self, ctx, ssrc):
+        """(rtcp_index, SRTCP replay lix, bitmap) of ssrc, None if none"""
+        r = ctypes.c_uint32()
+        x, b = ctypes.c_uint64(), ctypes.c_uint64()
+        if self.l.oracle_rtcp_state(ctx, ssrc, ctypes.byref(r),
+                                    ctypes.byref(x), ctypes.byref(b)):
+            return None
+        return (r.value, x.value, b.value)
+
+    def rtcp_set(self, ctx, ssrc, rtcp_index, lix, bitmap):
+        return self.l.oracle_rtcp_set(ctx, ssrc, rtcp_index, lix, bitmap)
 
     def call(self, ctx, opname, size, pos, end, inb, nout):
         mb = OMbuf()

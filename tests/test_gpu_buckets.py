@@ -12,7 +12,10 @@ the reference by the golden replays), through srtp_*_batch_dev:
   * a bucket over its capacity and a session over SGPU_BP_SEGMAX in one
     bucket: SPF_SEG, the radix-sort re-plan;
   * a forged packet the fold must reject (its s_l carried the next
-    packets' estimate): the host folds.
+    packets' estimate): the host folds;
+  * rejected plans (SPF_SEG, SPF_SSRC) in front of the general AES-CM
+    kernels (srtp_gpu_tune nolean, nomk, perclass), which nothing but the
+    plan's guard words keep from the descriptors dead buckets never wrote.
 
 Every case compares whole arenas, pos, end, errno and every session's
 exported state, and asserts which planner ran (srtp_gpu_counter "mplans",
@@ -80,20 +83,23 @@ def counters():
     return {c: P.counter(c) for c in COUNTERS}
 
 
-def run_modes(torch, suite, nsess, batches, forged=None, modes=None):
+def run_modes(torch, suite, nsess, batches, forged=None, modes=None,
+              knobs=None):
     """run every batch (protect, then unprotect with the forged packets of
-    forged[bi]) in each mode; returns {mode: (outs, tx states, rx states,
-    counter deltas per call)}"""
+    forged[bi]) in each mode, under the srtp_gpu_tune knobs `knobs` beside
+    the mode's own; returns {mode: (outs, tx states, rx states, counter
+    deltas per call)}"""
     keys = keys_for(suite, nsess)
     res = {}
     for mode in modes or ("bucket", "count", "general"):
         # bucket_copy: the outcome back by a blit copy, not by k_bp_finish
-        knobs = ({"nobucket": 1} if mode == "count" else
-                 {"nopost": 1} if mode == "bucket_copy" else {})
+        mk = dict(knobs or {})
+        mk.update({"nobucket": 1} if mode == "count" else
+                  {"nopost": 1} if mode == "bucket_copy" else {})
         tx = [P.Srtp(suite, k) for k in keys]
         rx = [P.Srtp(suite, k) for k in keys]
         outs, deltas = [], []
-        with P.tune(**knobs):
+        with P.tune(**mk):
             for bi, pk in enumerate(batches):
                 arena, pos, end, cap, sess = to_arena(pk)
                 c0 = counters()
@@ -242,3 +248,54 @@ def test_bucket_fold_rejected_falls_back(torch_cuda):
     # the device fold gave up (one host fold), the host engine folded
     # (it counts its own)
     assert d["mplans"] == 1 and d["folds"] >= 1 and d["devfolds"] == 0, d
+
+
+def second_ssrc(pk, k):
+    """packet k of the batch under another SSRC"""
+    s, q = pk[k]
+    return pk[:k] + [(s, q[:8] + (0x7fff0000 + s).to_bytes(4, "big") +
+                      q[12:])] + pk[k + 1:]
+
+
+@pytest.mark.parametrize("suite", [1, 5])
+@pytest.mark.parametrize("knob", ["nolean", "nomk", "perclass"])
+def test_bucket_rejected_plan_general_kernels(suite, knob, torch_cuda):
+    """the general AES-CM kernels (k_ctr_hmac_any; perclass: k_ctr_hmac per
+    class) behind a rejected bucket plan.  skip[] holds packet 0's class
+    alone and the rejection is the plan's fail word, so these kernels must
+    heed that word as the lean ones do: nothing runs over the order[] and
+    desc[] entries dead buckets never wrote, the host re-plans, everything
+    equals the general engine.
+
+    SPF_SEG: one session carries half of 3000 packets (over SGPU_BP_SEGMAX
+    in its bucket), re-planned by the radix grouping; the uniform batch
+    behind it takes the buckets again.  SPF_SSRC: 300 sessions of three
+    packets, one packet of one session under a second SSRC.  (Nothing
+    follows that one: the session now has two streams, stream.c:70-109, and
+    the many-session planners take sessions of one stream only.)"""
+    rng = np.random.default_rng(909 + suite)
+    nsess = 512
+    s0 = [65000] * nsess
+    p0 = np.full(nsess, 0.5 / (nsess - 1))
+    p0[0] = 0.5
+    b0, last = traffic(rng, 3000, p0, s0, plen=(0, 41))
+    b1, _ = traffic(rng, 3000, np.full(nsess, 1.0 / nsess), s0, last,
+                    plen=(0, 41))
+    res = run_modes(torch_cuda, suite, nsess, [b0, b1],
+                    modes=("bucket", "general"), knobs={knob: 1})
+    d = res["bucket"][3]
+    for dr in range(2):
+        assert d[0][dr]["rejects"] == 1 and d[0][dr]["mplans"] == 1, d
+        assert d[1][dr]["rejects"] == 0 and d[1][dr]["mplans"] == 1, d
+
+    nsess = 300
+    pk = [(s, rtp_packet(rng, 500 + q, 0x7000 + s, plen=50))
+          for s in range(nsess) for q in range(3)]
+    pk = second_ssrc(pk, 3 * 117 + 1)
+    res = run_modes(torch_cuda, suite, nsess, [pk],
+                    modes=("bucket", "general"), knobs={knob: 1})
+    d = res["bucket"][3][0]
+    for dr in range(2):
+        assert d[dr]["rejects"] == 1 and d[dr]["mplans"] == 0, d
+    err = res["bucket"][0][0]
+    assert not err[0][3].any() and not err[1][3].any()
