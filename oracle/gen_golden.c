@@ -526,6 +526,137 @@ static void scn_srtcp_truncations(int suite)
 	scn_end();
 }
 
+/*
+ * Header geometry: RTP headers of 12 .. 268 bytes (rtp_hdr_decode,
+ * src/rtp/rtp.c:88-137: 12 + 4*CC +, with X set, 4 + 4*length), about eight
+ * per class (hl >> 2) & 3, among them headers of one, two and four 64-byte
+ * chunks.  CSRCs alone up to 72 bytes, CC = 15 plus an extension above;
+ * 28 and 76 also as CC = 0 plus an extension (76 has no CSRC-only form: its
+ * first form is CC = 15 with an empty extension).  Payloads of 0 and, up to
+ * a header of 140 bytes, 33 bytes.  One sender protects every packet (one run of calls), then one
+ * receiver takes each protected packet, a tampered copy and, once per shape,
+ * a copy cut inside the extension (the CSRC list where there is none).
+ *
+ * Its random bytes come from a generator state of its own, so every other
+ * record of the file stays what it was before this scenario existed.
+ */
+static const struct { unsigned cc; int ext; unsigned xlen; } hdr_shape_alt[2] = {
+	{0, 1, 3}, {0, 1, 15},
+};
+
+static uint64_t hs_rng = 0x4844525348415045ull;
+
+static void scn_header_shapes(int suite)
+{
+	enum { NSHAPE = 33, NPKT = 2 * NSHAPE };
+	static const size_t plens[2] = {0, 33};
+	static uint8_t key[46], p[1024];
+	static uint8_t *prot[NPKT];
+	static size_t prot_off[NPKT], prot_end[NPKT], cut[NPKT];
+	unsigned cc[NSHAPE], xlen[NSHAPE];
+	int ext[NSHAPE];
+	char name[64];
+	uint64_t saved = rng_s;
+	uint32_t ssrc;
+	uint16_t seq = 65500;   /* the ROC wraps inside */
+	size_t hl, i;
+	int tx, rx, ns = 0, k;
+
+	rng_s = hs_rng;
+
+	for (hl = 12; hl <= 268; hl += 4) {
+		if ((hl > 92 && hl < 124) || (hl > 140 && hl < 252))
+			continue;
+		cc[ns] = hl <= 72 ? (unsigned)(hl - 12) / 4 : 15;
+		ext[ns] = hl > 72;
+		xlen[ns] = hl > 72 ? (unsigned)(hl - 76) / 4 : 0;
+		ns++;
+		if (hl == 28 || hl == 76) {
+			cc[ns] = hdr_shape_alt[hl == 76].cc;
+			ext[ns] = hdr_shape_alt[hl == 76].ext;
+			xlen[ns] = hdr_shape_alt[hl == 76].xlen;
+			ns++;
+		}
+	}
+	if (ns != NSHAPE) {
+		fprintf(stderr, "header shapes: %d\n", ns);
+		exit(1);
+	}
+
+	for (i = 0; i < sizeof(key); i++)
+		key[i] = (uint8_t)rnd();
+	ssrc = (uint32_t)rnd();
+
+	snprintf(name, sizeof(name), "srtp_header_shapes_s%d", suite);
+	scn_begin(name);
+	tx = ctx_add(suite, key, keylen[suite] + saltlen[suite], 0);
+	rx = ctx_add(suite, key, keylen[suite] + saltlen[suite], 0);
+	ctxs_emit_and_open_ops();
+
+	for (k = 0; k < NPKT; k++) {
+		int s = k / 2, err;
+		size_t off = 4 * (size_t)(k % 4), n, e2;
+		size_t h = 12 + 4 * cc[s] + (ext[s] ? 4 + 4 * xlen[s] : 0);
+
+		prot[k] = NULL;
+		if (k % 2 && h > 140)   /* keeps the fixture small */
+			continue;
+		memset(p, 0, off);
+		n = off + build_rtp(p + off, seq++, (uint32_t)rnd(), ssrc,
+				    cc[s], ext[s], xlen[s], plens[k % 2], 1);
+		prot[k] = run_op(tx, OP_SRTP_ENC, p, n + 32, off, n, &err,
+				 NULL, &e2);
+		if (err) {
+			fprintf(stderr, "header shapes: protect %d\n", err);
+			exit(1);
+		}
+		prot_off[k] = off;
+		prot_end[k] = e2;
+		/* inside the extension body, else inside its 4-byte header,
+		   else inside the CSRC list, else inside the fixed header */
+		if (ext[s] && xlen[s])
+			cut[k] = h - 2 * xlen[s] - 1;
+		else if (ext[s])
+			cut[k] = h - 2;
+		else if (cc[s])
+			cut[k] = 12 + 2 * cc[s] + 1;
+		else
+			cut[k] = 7;
+	}
+
+	for (k = 0; k < NPKT; k++) {
+		size_t off = prot_off[k], e2 = prot_end[k], at;
+		uint8_t *c = prot[k];
+
+		if (!c)
+			continue;
+		free(run_op(rx, OP_SRTP_DEC, c, e2, off, e2, NULL, NULL,
+			    NULL));
+		/* tampered: header, payload (the tag where there is none)
+		   and tag in turn */
+		switch (k % 3) {
+		case 0:  at = off + 12 + rndn((uint32_t)(cut[k] > 12 ?
+						 cut[k] - 12 : 1)); break;
+		case 1:  at = e2 - taglen[suite] - (k % 2 ? 1 + rndn(33) : 0);
+			 break;
+		default: at = e2 - 1 - rndn((uint32_t)taglen[suite]); break;
+		}
+		if (at < off + 4 || at >= e2)
+			at = e2 - 1;
+		c[at] ^= (uint8_t)(1u << rndn(8));
+		free(run_op(rx, OP_SRTP_DEC, c, e2, off, e2, NULL, NULL,
+			    NULL));
+		if (k % 2 == 0)
+			free(run_op(rx, OP_SRTP_DEC, c, off + cut[k], off,
+				    off + cut[k], NULL, NULL, NULL));
+		free(c);
+	}
+	scn_end();
+
+	hs_rng = rng_s;
+	rng_s = saved;
+}
+
 /* srtp_alloc argument validation (srtp.c:98-158) */
 static void alloc_errors(void)
 {
@@ -690,6 +821,8 @@ int main(void)
 		scn_srtcp_truncations(s);
 	}
 	scn_random_srtcp(1, 0, 3, 40);      /* > 8 SSRCs */
+	for (s = 0; s < 6; s++)
+		scn_header_shapes(s);
 
 	alloc_errors();
 	prim_kdf();
