@@ -657,6 +657,132 @@ static void scn_header_shapes(int suite)
 	rng_s = saved;
 }
 
+/*
+ * rtcp-mux: one context carries RTP and RTCP, and both share its table of
+ * eight streams (stream_get_seq / stream_get, src/srtp/stream.c:29-109).  A
+ * sender and a receiver, srtp_* and srtcp_* calls interleaved per call:
+ *   - a stream created by RTP and then used by SRTCP, and one created by
+ *     SRTCP and then used by RTP (its s_l is the first RTP seq);
+ *   - three SSRCs at random, some packets tampered or delivered twice;
+ *   - SSRCs four to seven, created by RTP and by SRTCP in turn;
+ *   - a forged SRTCP packet from a new SSRC, which takes the receiver's
+ *     last slot (the lookup runs before the tag check, srtcp.c:163);
+ *   - a ninth and a tenth SSRC: ENOSR from an RTP call and from an RTCP
+ *     call, on the sender and (the packets as they are) on the receiver;
+ *   - the eighth stream's genuine packets and the older streams afterwards.
+ * Payloads and RTCP bodies of at most 64 bytes.
+ *
+ * Like the header shapes it draws from a generator state of its own.
+ */
+static uint64_t mux_rng = 0x5254434d55585f31ull;
+
+enum { MUX_PLAIN, MUX_FORGE, MUX_TWICE };
+
+static void mux_send(int tx, int rx, int rtcp, uint32_t ssrc, uint16_t seq,
+		     int how)
+{
+	static uint8_t p[256];
+	const enum opk enc = rtcp ? OP_SRTCP_ENC : OP_SRTP_ENC;
+	const enum opk dec = rtcp ? OP_SRTCP_DEC : OP_SRTP_DEC;
+	size_t off = 4 * (size_t)rndn(2), n, e2;
+	uint8_t *c;
+	int err;
+
+	memset(p, 0, off);
+	if (rtcp)
+		n = off + build_rtcp(p + off, ssrc, 4 * (size_t)rndn(8));
+	else
+		n = off + build_rtp(p + off, seq, (uint32_t)rnd(), ssrc,
+				    rndn(4) == 0 ? 1 + rndn(2) : 0, 0, 0,
+				    rndn(8) == 0 ? 64 : rndn(25), 1);
+	c = run_op(tx, enc, p, n + 64, off, n, &err, NULL, &e2);
+	if (err) {
+		/* the sender has no slot left: the receiver gets the packet
+		   as it is */
+		free(c);
+		free(run_op(rx, dec, p, n, off, n, NULL, NULL, NULL));
+		return;
+	}
+	if (how == MUX_FORGE)
+		c[e2 - 1 - rndn(4)] ^= (uint8_t)(1u << rndn(8));
+	free(run_op(rx, dec, c, e2, off, e2, NULL, NULL, NULL));
+	if (how == MUX_TWICE)
+		free(run_op(rx, dec, c, e2, off, e2, NULL, NULL, NULL));
+	free(c);
+}
+
+static void scn_rtcp_mux(int suite)
+{
+	static uint8_t key[46];
+	uint64_t saved = rng_s;
+	uint32_t ssrc[10];
+	uint16_t seq[10];
+	char name[64];
+	int tx, rx, i, k;
+	size_t j;
+
+	rng_s = mux_rng;
+
+	for (j = 0; j < sizeof(key); j++)
+		key[j] = (uint8_t)rnd();
+	for (i = 0; i < 10; i++) {
+		ssrc[i] = (uint32_t)rnd();
+		seq[i] = i ? (uint16_t)rnd() : 65530;   /* the ROC wraps */
+	}
+
+	snprintf(name, sizeof(name), "srtp_rtcp_mux_s%d", suite);
+	scn_begin(name);
+	tx = ctx_add(suite, key, keylen[suite] + saltlen[suite], 0);
+	rx = ctx_add(suite, key, keylen[suite] + saltlen[suite], 0);
+	ctxs_emit_and_open_ops();
+
+	/* created by RTP, then used by SRTCP */
+	for (i = 0; i < 3; i++)
+		mux_send(tx, rx, 0, ssrc[0], seq[0]++, MUX_PLAIN);
+	for (i = 0; i < 3; i++)
+		mux_send(tx, rx, 1, ssrc[0], 0, MUX_PLAIN);
+	/* created by SRTCP, then used by RTP */
+	for (i = 0; i < 3; i++)
+		mux_send(tx, rx, 1, ssrc[1], 0, MUX_PLAIN);
+	for (i = 0; i < 3; i++)
+		mux_send(tx, rx, 0, ssrc[1], seq[1]++, MUX_PLAIN);
+
+	for (i = 0; i < 60; i++) {
+		int rtcp = (int)rndn(2);
+		int how = (int)rndn(12);
+		k = (int)rndn(3);
+		mux_send(tx, rx, rtcp, ssrc[k], rtcp ? 0 : seq[k]++,
+			 how == 0 ? MUX_FORGE : how == 1 ? MUX_TWICE :
+			 MUX_PLAIN);
+	}
+
+	for (k = 3; k < 7; k++) {
+		mux_send(tx, rx, k & 1, ssrc[k], seq[k]++, MUX_PLAIN);
+		mux_send(tx, rx, !(k & 1), ssrc[k], seq[k]++, MUX_PLAIN);
+		mux_send(tx, rx, k & 1, ssrc[k], seq[k]++, MUX_TWICE);
+	}
+
+	/* the receiver's last slot goes to a forged SRTCP packet */
+	mux_send(tx, rx, 1, ssrc[7], 0, MUX_FORGE);
+
+	mux_send(tx, rx, 0, ssrc[8], seq[8]++, MUX_PLAIN);
+	mux_send(tx, rx, 1, ssrc[8], 0, MUX_PLAIN);
+	mux_send(tx, rx, 1, ssrc[9], 0, MUX_PLAIN);
+	mux_send(tx, rx, 0, ssrc[9], seq[9]++, MUX_PLAIN);
+
+	mux_send(tx, rx, 1, ssrc[7], 0, MUX_PLAIN);
+	mux_send(tx, rx, 0, ssrc[7], seq[7]++, MUX_PLAIN);
+	mux_send(tx, rx, 1, ssrc[7], 0, MUX_TWICE);
+	for (k = 0; k < 7; k++) {
+		mux_send(tx, rx, 0, ssrc[k], seq[k]++, MUX_PLAIN);
+		mux_send(tx, rx, 1, ssrc[k], 0, MUX_PLAIN);
+	}
+	scn_end();
+
+	mux_rng = rng_s;
+	rng_s = saved;
+}
+
 /* srtp_alloc argument validation (srtp.c:98-158) */
 static void alloc_errors(void)
 {
@@ -823,6 +949,8 @@ int main(void)
 	scn_random_srtcp(1, 0, 3, 40);      /* > 8 SSRCs */
 	for (s = 0; s < 6; s++)
 		scn_header_shapes(s);
+	for (s = 0; s < 6; s++)
+		scn_rtcp_mux(s);
 
 	alloc_errors();
 	prim_kdf();
