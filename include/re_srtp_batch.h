@@ -286,7 +286,9 @@ int srtp_alloc_many(struct srtp **srtpv, size_t n, enum srtp_suite suite,
  * thread takes this look-back epoch, its look-back words zeroed first),
  * "norxplan" (an unprotect batch, one stream or many sessions, whose device
  * plan was rejected for reordered or replayed packets goes straight to the
- * host engine, not to the device receive planner),
+ * host engine, not to the device receive planner), "nomrplan" (an SRTCP
+ * batch over many sessions on device windows goes through the host engine,
+ * not the many-session SRTCP planner),
  * "rxseq" (srtp_rx_index* and srtp_rx_fold walk
  * in one sequential pass, not in parallel parts), "freshmulti" (the
  * planner's first-batch hint: 1 sends a session's first batch to the
@@ -314,7 +316,9 @@ int srtp_gpu_tune(const char *name, long value);
  * (late packets it accepted), "rxdups" (EALREADY verdicts it gave),
  * "mrxplans" (reordered / duplicated many-session unprotect batches
  * completed by the bucket receive planner; "rxlate" and "rxdups" count its
- * packets too).  0 for an unknown name.
+ * packets too), "mrplans" (SRTCP batches over many sessions planned on the
+ * device; srtp_gpu_tune "nomrplan" sends them through the host engine).  0
+ * for an unknown name.
  */
 uint64_t srtp_gpu_counter(const char *name);
 

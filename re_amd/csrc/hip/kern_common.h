@@ -337,7 +337,9 @@ __device__ __forceinline__ bool rtcp_job(const KArgs &a,
 					 uint32_t p, uint64_t d, uint8_t vd,
 					 struct sgpu_job &j)
 {
-	const uint32_t comp = c.compmap[0];
+	/* per-packet keys behind the many-session planner (sess: session ->
+	 * SRTCP component), one key otherwise */
+	const uint32_t comp = c.compmap[c.sess ? c.sess[p] : 0u];
 	const struct sgpu_comp *cp = a.comps + comp;
 	const uint32_t off = c.pos[p];
 	const uint32_t L = c.end[p] - off;

@@ -413,6 +413,14 @@ static int run_dev(int op, struct srtp **sessv, size_t nsess,
 		if (r >= 0)
 			return r;
 	}
+	/* SRTCP over many sessions, up to 8 SSRCs each: the bucket planner
+	 * over the host's stream tables (current after sess_host) */
+	if ((op == OP_RTCP_ENC || op == OP_RTCP_DEC) && nsess > 1 && d->sess &&
+	    !g_env.noplan && !g_env.general && !g_env.nomrplan) {
+		int r = dev_mplanned_rtcp(op, sessv, nsess, d);
+		if (r >= 0)
+			return r;
+	}
 	return dev_staged(op, sessv, nsess, d);
 }
 

@@ -6,8 +6,10 @@
  * one stream by the separate planner kernels (dp_issue / dp_finish;
  * dev_planned picks among the three), reordered arrivals (plan_rx.hip),
  * several streams of one session (plan_streams.hip), SRTCP
- * (dev_planned_rtcp), many sessions with resident state (dev_mplanned) and
- * their reordered arrivals (plan_buckets_rx.hip, dev_mrxplanned).  Each call is a struct dcall between its launches
+ * (dev_planned_rtcp; many sessions with up to 8 SSRCs each:
+ * plan_buckets_rtcp.hip, dev_mplanned_rtcp), many sessions with resident
+ * state (dev_mplanned) and their reordered arrivals (plan_buckets_rx.hip,
+ * dev_mrxplanned).  Each call is a struct dcall between its launches
  * (*_issue) and its completion (*_finish), so the synchronous calls
  * (dev_call) and the asynchronous tickets (batch_async.c) share it.  Where a
  * call's arrays lie in the workspace pools: struct ws_layout (srtp_int.h)
@@ -1299,6 +1301,189 @@ int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 	return err;
 }
 
+/* ---- SRTCP, many sessions with up to 8 SSRCs each ---------------------- */
+
+#define BP_HEAD (512u + 4u * SGPU_BP_NBMAX)     /* w->bp: see below */
+
+static size_t al256(size_t x)
+{
+	return (x + 255) & ~(size_t)255;
+}
+
+/*
+ * An SRTCP protect / unprotect batch over many sessions, every array in
+ * HBM, planned by the bucket planner of plan_buckets_rtcp.hip against the
+ * host's stream tables (current: run_dev called sess_host; SRTCP state is
+ * not resident).  One pass over the sessions gathers the tables
+ * (mrplan_gather), one upload, sgpu_bplan_rtcp_scatter / _plan, the compact
+ * crypto kernels with per-packet keys guarded by the plan, _finish, one copy
+ * back of the touched tables, one synchronisation, the apply.
+ * 0: done; -1: a batch the geometry or the gather does not take (nothing
+ * counted), a rejected plan, or a forged packet (undone) -- nothing
+ * modified, the caller's fallback continues; errno.
+ *
+ * w->ms: cm | toff | recs (up); w->mscr: sinfo | sout (down); w->bp:
+ * BP_HEAD as dev_bplanned_issue lays it out (the bucket counters at 512,
+ * zero between calls) | bucket entries | fail words.
+ */
+int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
+		      struct srtp_batch_dev *d)
+{
+	const int prot = op == OP_RTCP_ENC;
+	const struct comp *c0 = &sessv[0]->rtcp;
+	const int gcm = c0->mode == SGPU_MODE_GCM;
+	const size_t n = d->n;
+	const uint32_t grow = 4u + c0->tag_len + (gcm ? 16u : 0u);
+	const size_t na = (n + SGPU_BP_BLOCK * SGPU_BP_PPT - 1) /
+			  (SGPU_BP_BLOCK * SGPU_BP_PPT);
+	const size_t o_toff = al256(nsess * 4);
+	const size_t o_recs = o_toff + al256((nsess + 1) * 4);
+	const size_t o_sout = al256(nsess * 4);
+	const size_t down = o_sout +
+			    nsess * SRTP_MAX_STREAMS * sizeof(struct sgpu_rtcp_rec);
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
+		.vs = n * 5 + 64, .cm = 4,
+		.pl = sizeof(struct sgpu_plan_out) + 64, .es = n * 4};
+	struct ws_layout L;
+	struct sgpu_bplan_rtcp R;
+	struct sgpu_compact C;
+	struct sgpu_plan_out *po, *po_d;
+	uint32_t *toff_h, bshift, nb, cap;
+	size_t up;
+	void *stream = d->stream;
+	struct ws *w;
+	const int times = g_env.times;
+	double t[4];
+	int err;
+
+	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
+		return -1;
+	w = ws_get();
+	if (!w)
+		return ENOMEM;
+	err = ws_layout_reserve(w, n, &z, &L);
+	if (!err)
+		err = pool_reserve(w, &w->ms, o_recs + nsess * SRTP_MAX_STREAMS *
+				   sizeof(struct sgpu_rtcp_rec));
+	if (!err)
+		err = pool_reserve(w, &w->mscr, down);
+	if (!err)
+		err = pool_reserve(w, &w->bp, BP_HEAD +
+				   al256((size_t)nb * cap * 16) + al256(na * 4));
+	if (err)
+		return err;
+	toff_h = (uint32_t *)(w->ms.h + o_toff);
+	t[0] = times ? now_ms() : 0;
+	if (mrplan_gather(sessv, nsess, prot, toff_h,
+			  (struct sgpu_rtcp_rec *)(w->ms.h + o_recs),
+			  (uint32_t *)w->ms.h))
+		return -1;
+	up = o_recs + (size_t)toff_h[nsess] * sizeof(struct sgpu_rtcp_rec);
+	t[1] = times ? now_ms() : 0;
+	if (w->bp_d != w->bp.d) {
+		/* a new pool (or a call that did not finish): counters from
+		 * zero */
+		err = sgpu_memset(w->bp.d, 0, BP_HEAD, stream);
+		if (err)
+			return err;
+		w->bp_d = w->bp.d;
+	}
+	po = (struct sgpu_plan_out *)w->pl.h;
+	po_d = (struct sgpu_plan_out *)w->pl.d;
+	memset(&R, 0, sizeof(R));
+	rplan_in(&R.in, sessv[0], (uint32_t)n, prot);
+	R.in.ssrc_any = 0;
+	R.in.ssrc = R.in.rtcp_index = 0;
+	R.in.lix = R.in.bitmap = 0;
+	R.nsess = (uint32_t)nsess;
+	R.bshift = bshift;
+	R.nb = nb;
+	R.cap = cap;
+	R.delta = prot ? (int32_t)grow : -(int32_t)grow;
+	R.pos = d->pos;
+	R.end = d->end;
+	R.capv = d->cap;
+	R.sess = d->sess;
+	R.endw = d->end;
+	R.err = d->err;
+	R.es = L.es;
+	R.hdr = L.hdr;
+	R.desc = L.desc;
+	R.bcount = (uint32_t *)(w->bp.d + 512);
+	R.tmp = (void *)(w->bp.d + BP_HEAD);
+	R.afail = (uint32_t *)(w->bp.d + BP_HEAD + al256((size_t)nb * cap * 16));
+	R.toff = (const uint32_t *)(w->ms.d + o_toff);
+	R.recs = (const struct sgpu_rtcp_rec *)(w->ms.d + o_recs);
+	R.sinfo = (uint32_t *)w->mscr.d;
+	R.sout = (struct sgpu_rtcp_rec *)(w->mscr.d + o_sout);
+	R.out = po_d;
+	R.nfail = L.nfail;
+	R.outbytes = (uint32_t)offsetof(struct sgpu_plan_out, tail_ix);
+	R.outh = g_env.nopost ? NULL : (uint32_t *)po;
+	srv_stop(w);
+	err = sgpu_memcpy_h2d(w->ms.d, w->ms.h, up, stream);
+	if (!err)
+		err = sgpu_bplan_rtcp_scatter(d->arena, d->arena_size, &R, stream);
+	if (!err)
+		err = sgpu_bplan_rtcp_plan(&R, stream);
+	/* the compact kernels' SRTCP form with per-packet keys (AES-CM: class
+	 * 2, the cipher region starts at byte 8), guarded by the plan */
+	C = compact_of(d, &L);
+	C.compmap = (const uint32_t *)w->ms.d;
+	C.sess = d->sess;
+	C.rtcp = 1;
+	C.guard = &po_d->fail;
+	if (!err)
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, gcm ? 0 : 2, prot, stream);
+	if (!err)
+		err = sgpu_bplan_rtcp_finish(&R, stream);
+	if (!err && g_env.nopost)
+		err = sgpu_memcpy_d2h(po, po_d, R.outbytes, stream);
+	if (!err)
+		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, down, stream);
+	t[2] = times ? now_ms() : 0;
+	if (!err)
+		err = sgpu_stream_sync(stream);
+	t[3] = times ? now_ms() : 0;
+	if (err) {
+		sgpu_stream_sync(stream);       /* no copy still reads ms.h */
+		w->bp_d = NULL;
+		return err;
+	}
+	if (po->fail) {
+		/* the crypto launch and the results did nothing */
+		count(&g_cnt_rejects, 1);
+		if (g_env.times)
+			fprintf(stderr, "re_srtp mrtcp plan n=%zu nsess=%zu %s: "
+				"rejected (SPF %#x)\n", n, nsess,
+				prot ? "protect" : "unprotect", po->fail);
+		return -1;
+	}
+	count(&g_cnt_mrplans, 1);
+	if (po->nfail) {
+		/* a forged packet: undo on the device (no result was written,
+		 * the host's tables are as they were), fold on the host engine */
+		count(&g_cnt_misses, po->nfail);
+		count(&g_cnt_folds, 1);
+		C.undo = 1;
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, gcm ? 0 : 2, 0, stream);
+		if (!err)
+			err = sgpu_stream_sync(stream);
+		return err ? err : -1;
+	}
+	mrplan_apply(sessv, nsess, prot, (const uint32_t *)w->mscr.h,
+		     (const struct sgpu_rtcp_rec *)(w->mscr.h + o_sout));
+	if (times)
+		fprintf(stderr, "re_srtp mrtcp plan n=%zu nsess=%zu %s: gather "
+			"%.3f submit %.3f wait %.3f apply %.3f ms\n", n, nsess,
+			prot ? "protect" : "unprotect", t[1] - t[0], t[2] - t[1],
+			t[3] - t[2], now_ms() - t[3]);
+	return 0;
+}
+
 /*
  * Many sessions with at most one RTP stream each, every array in HBM: the
  * multi-session device planner (plan_multi.hip) plus the compact kernels
@@ -1340,8 +1525,6 @@ static int mfold(struct dcall *k, int phase, const uint32_t *nfail,
  * between calls) | bucket entries | sorted | fail words | sseg | sout |
  * launch order
  */
-#define BP_HEAD (512u + 4u * SGPU_BP_NBMAX)
-
 static int dev_bplanned_issue(struct dcall *k, uint32_t bshift, uint32_t nb,
 			      uint32_t cap)
 {

@@ -694,6 +694,154 @@ int mplan_gather_res(struct srtp **sessv, size_t nsess,
 	return 0;
 }
 
+/* ---- many-session SRTCP device plan (dev_mplanned_rtcp) ---------------- */
+
+struct mrg {
+	struct srtp **sessv;
+	uint32_t *toff, *cm;
+	struct sgpu_rtcp_rec *recs;
+	const struct sgpu_rtcp_rec *sout;
+	const uint32_t *sinfo;
+	int prot, hmac;
+	uint32_t epoch;
+	atomic_int bad;
+};
+
+/* pass 1: the sessions a plan can take, the slot map, the table sizes */
+static void mrplan_count_part(void *arg, size_t a, size_t b)
+{
+	struct mrg *g = arg;
+	const struct srtp *s0 = g->sessv[0];
+	size_t k;
+	for (k = a; k < b; k++) {
+		struct srtp *s = g->sessv[k];
+		unsigned i;
+		if (k + 16 < b)
+			__builtin_prefetch(g->sessv[k + 16], 0, 1);
+		/* one suite and one SRTP_UNENCRYPTED_SRTCP: one kernel class,
+		 * one E bit, one trailer length */
+		if (s->suite != s0->suite || s->rtcp.has_aes != s0->rtcp.has_aes ||
+		    s->rtcp.encrypted != s0->rtcp.encrypted ||
+		    s->nstreams > SRTP_MAX_STREAMS) {
+			atomic_store(&g->bad, 1);
+			return;
+		}
+		/* two sessv entries naming one context (mplan_gather_part) */
+		if (__atomic_exchange_n(&s->mp_epoch, g->epoch,
+					__ATOMIC_RELAXED) == g->epoch) {
+			atomic_store(&g->bad, 1);
+			return;
+		}
+		/* the records hold 32 bits of the window's top (an imported
+		 * one may lie higher: the host's replay_check takes it) */
+		if (!g->prot && g->hmac)
+			for (i = 0; i < s->nstreams; i++)
+				if (s->streams[i].replay_rtcp.lix > 0x7fffffffu) {
+					atomic_store(&g->bad, 1);
+					return;
+				}
+		g->cm[k] = s->rtcp.dev;                 /* comp[1] = RTCP */
+		g->toff[k + 1] = s->nstreams;
+	}
+}
+
+/* pass 2: the stream records behind their offsets */
+static void mrplan_fill_part(void *arg, size_t a, size_t b)
+{
+	struct mrg *g = arg;
+	size_t k;
+	for (k = a; k < b; k++) {
+		const struct srtp *s = g->sessv[k];
+		struct sgpu_rtcp_rec *r = g->recs + g->toff[k];
+		unsigned i;
+		if (k + 16 < b)
+			__builtin_prefetch(g->sessv[k + 16], 0, 1);
+		for (i = 0; i < s->nstreams; i++) {
+			const struct srtp_stream *x = &s->streams[i];
+			r[i].ssrc = x->ssrc;
+			r[i].ix = g->prot ? x->rtcp_index
+					  : (uint32_t)x->replay_rtcp.lix;
+			r[i].blo = (uint32_t)x->replay_rtcp.bitmap;
+			r[i].bhi = (uint32_t)(x->replay_rtcp.bitmap >> 32);
+		}
+	}
+}
+
+/*
+ * The sessions' stream tables for the many-session SRTCP planner: toff
+ * (nsess + 1 offsets), recs (the streams in table order, at most 8 per
+ * session), cm (session -> SRTCP component).  -1: not a batch it takes
+ * (sessions of different suites or SRTP_UNENCRYPTED_SRTCP, one context
+ * named twice, a window beyond 31 bits); nothing is modified either way.
+ */
+int mrplan_gather(struct srtp **sessv, size_t nsess, int prot, uint32_t *toff,
+		  struct sgpu_rtcp_rec *recs, uint32_t *cm)
+{
+	struct mrg g = {.sessv = sessv, .toff = toff, .cm = cm, .recs = recs,
+			.prot = prot, .hmac = sessv[0]->rtcp.has_hmac};
+	size_t k;
+	do {
+		g.epoch = __atomic_add_fetch(&g_epoch, 1, __ATOMIC_RELAXED);
+	} while (!g.epoch);
+	toff[0] = 0;
+	par_for(nsess, mplan_par(), mrplan_count_part, &g);
+	if (atomic_load(&g.bad))
+		return -1;
+	for (k = 0; k < nsess; k++)
+		toff[k + 1] += toff[k];
+	par_for(nsess, mplan_par(), mrplan_fill_part, &g);
+	return 0;
+}
+
+static void mrplan_apply_part(void *arg, size_t a, size_t b)
+{
+	struct mrg *g = arg;
+	size_t k;
+	for (k = a; k < b; k++) {
+		const uint32_t si = g->sinfo[k];
+		const uint32_t nst = si & 0xffu, mask = si >> 8 & 0xffu;
+		const struct sgpu_rtcp_rec *o = g->sout + k * SRTP_MAX_STREAMS;
+		struct srtp *s;
+		unsigned i;
+		if (k + 16 < b && g->sinfo[k + 16])
+			__builtin_prefetch(g->sessv[k + 16], 1, 1);
+		if (!si)
+			continue;
+		s = g->sessv[k];
+		for (i = 0; i < nst && i < SRTP_MAX_STREAMS; i++) {
+			struct srtp_stream *x = &s->streams[i];
+			if (i >= s->nstreams) {
+				/* stream_new (stream.c:45-67) */
+				memset(x, 0, sizeof(*x));
+				x->ssrc = o[i].ssrc;
+			}
+			if (!(mask >> i & 1u))
+				continue;
+			if (g->prot) {
+				x->rtcp_index = o[i].ix;
+			}
+			else if (g->hmac) {
+				x->replay_rtcp.lix = o[i].ix;
+				x->replay_rtcp.bitmap = (uint64_t)o[i].bhi << 32 |
+							o[i].blo;
+			}
+		}
+		if (nst > s->nstreams)
+			s->nstreams = nst < SRTP_MAX_STREAMS ? nst
+							     : SRTP_MAX_STREAMS;
+	}
+}
+
+/* the touched sessions' tables after an accepted plan (sinfo, sout: pinned
+ * copies of the planner's) into the host's */
+void mrplan_apply(struct srtp **sessv, size_t nsess, int prot,
+		  const uint32_t *sinfo, const struct sgpu_rtcp_rec *sout)
+{
+	struct mrg g = {.sessv = sessv, .sinfo = sinfo, .sout = sout,
+			.prot = prot, .hmac = sessv[0]->rtcp.has_hmac};
+	par_for(nsess, mplan_par(), mrplan_apply_part, &g);
+}
+
 static void mplan_apply_part(void *arg, size_t a, size_t b)
 {
 	struct mpg *g = arg;

@@ -127,6 +127,10 @@ struct srtp_env {
 				   the receive planner (one stream:
 				   plan_rx.hip; many sessions:
 				   plan_buckets_rx.hip) */
+	int nomrplan;           /* srtp_gpu_tune nomrplan: many-session SRTCP
+				   batches on device windows go through the
+				   host engine (dev_staged), not the bucket
+				   planner (plan_buckets_rtcp.hip) */
 	int smallsync;          /* srtp_gpu_tune smallsync: wait for a small
 				   launch by a stream synchronisation, not
 				   its completion word */
@@ -284,7 +288,7 @@ extern uint64_t g_cnt_pcbatch, g_cnt_pcpkts, g_cnt_pcfused, g_cnt_rxw_redo;
 extern uint64_t g_cnt_misses, g_cnt_folds, g_cnt_rejects, g_cnt_devfolds;
 extern uint64_t g_cnt_splans, g_cnt_fused, g_cnt_gated;
 extern uint64_t g_cnt_dplans, g_cnt_mplans, g_cnt_rplans, g_cnt_lbtimeout;
-extern uint64_t g_cnt_lplans;
+extern uint64_t g_cnt_lplans, g_cnt_mrplans;
 extern uint64_t g_cnt_rxplans, g_cnt_rxlate, g_cnt_rxdups, g_cnt_mrxplans;
 extern int g_fresh_multi;       /* srtp.c: the last first batch of a session
 				   showed several SSRCs (see there) */
@@ -476,6 +480,10 @@ int mplan_gather_res(struct srtp **sessv, size_t nsess,
 			    struct sgpu_sstate *st, uint32_t *cm,
 			    uint8_t *need, uint32_t *nup, uint64_t pend,
 			    uint64_t done);
+int mrplan_gather(struct srtp **sessv, size_t nsess, int prot, uint32_t *toff,
+		  struct sgpu_rtcp_rec *recs, uint32_t *cm);
+void mrplan_apply(struct srtp **sessv, size_t nsess, int prot,
+		  const uint32_t *sinfo, const struct sgpu_rtcp_rec *sout);
 int run_classes(uint8_t *arena, uint64_t asz, struct sgpu_compact C,
 		       const struct comp *c0, struct sgpu_plan_out *po_d,
 		       int prot, void *stream);
@@ -494,6 +502,8 @@ int dev_splanned_issue(struct dcall *k);
 int dev_splanned_finish(struct dcall *k);
 int dev_splanned(int op, struct srtp *s, struct srtp_batch_dev *d);
 int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d);
+int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
+		      struct srtp_batch_dev *d);
 int dev_mplanned_issue(struct dcall *k);
 int dev_mplanned_finish(struct dcall *k);
 int dev_mplanned_(int op, struct srtp **sessv, size_t nsess,

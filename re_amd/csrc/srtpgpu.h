@@ -792,6 +792,75 @@ struct sgpu_rfused {
 int   sgpu_run_rpplan(const uint8_t *arena, uint64_t arena_size,
 		      const struct sgpu_rfused *r, void *stream);
 
+/*
+ * SRTCP batches over many sessions with up to 8 SSRCs each, planned on the
+ * device in three launches around the crypto (plan_buckets_rtcp.hip; the
+ * rule per session: hip/plan_rtcp_seg.h), with the bucket geometry of
+ * sgpu_bplan_geometry:
+ *   sgpu_bplan_rtcp_scatter  per packet: the RTCP parse (hdr: the SSRC, 8),
+ *                            the window checks, the end copy, unprotect: the
+ *                            E || index word; its entry into its session's
+ *                            bucket.  Its first workgroup zeroes out->fail,
+ *                            out->nfail and *nfail
+ *   sgpu_bplan_rtcp_plan     per bucket (one workgroup, in LDS): the
+ *                            sessions' stream tables (toff / recs), the
+ *                            entries grouped by session and ranked by packet
+ *                            index, the stream slot of every packet (new
+ *                            SSRCs in first-appearance order), rank and
+ *                            predecessor per stream, the rule, desc, each
+ *                            touched session's table after the batch (sout,
+ *                            sinfo); a failed check: out->fail |=
+ *   (the compact crypto kernels, rtcp = 1, per-packet keys through sess and
+ *   cm, guarded by out->fail, counting their tag misses in *nfail)
+ *   sgpu_bplan_rtcp_finish   if !out->fail and !*nfail: end / err per
+ *                            packet; always: bcount back to zero,
+ *                            out->nfail, and outbytes from out to outh
+ * out->fail or out->nfail after it: nothing of the caller's was modified but
+ * the packets the crypto launches processed (undo: the same kernels,
+ * sgpu_compact undo).  bcount must be zero before the first launch of a
+ * workspace; every call leaves it so.
+ */
+struct sgpu_rtcp_rec {          /* hip/plan_rtcp_seg.h struct rseg_rec */
+	uint32_t ssrc;
+	uint32_t ix;            /* rtcp_index (protect), replay_rtcp.lix */
+	uint32_t blo, bhi;      /* replay_rtcp.bitmap */
+};
+
+struct sgpu_bplan_rtcp {
+	struct sgpu_rplan_in in;        /* n, prot, tag, gcm, hmac, encrypted,
+					   need, maxlen */
+	uint32_t nsess;
+	uint32_t bshift, nb, cap;       /* bucket geometry */
+	int32_t delta;                  /* end change of a processed packet */
+	const uint32_t *pos, *end, *capv, *sess;
+	uint32_t *endw;                 /* = end (results) */
+	int32_t *err;
+	uint32_t *es;                   /* end before the call */
+	struct sgpu_hdr *hdr;
+	uint64_t *desc;
+	uint4_t_ *tmp;                  /* nb x cap bucket entries: packet index,
+					   session in bucket | parsed << 8 |
+					   length << 16, SSRC, E || index */
+	uint32_t *bcount;               /* nb: entries per bucket (zeroed) */
+	uint32_t *afail;                /* per scatter workgroup */
+	const uint32_t *toff;           /* nsess + 1: session s's streams are
+					   recs[toff[s] .. toff[s + 1]) */
+	const struct sgpu_rtcp_rec *recs;
+	struct sgpu_rtcp_rec *sout;     /* nsess x 8: the tables after */
+	uint32_t *sinfo;                /* nsess: streams after the batch |
+					   the touched streams' bits << 8
+					   (0: the session had no packet) */
+	struct sgpu_plan_out *out;
+	uint32_t *nfail;                /* the crypto launch's miss counter */
+	uint32_t *outh;                 /* or NULL: outbytes from out to this
+					   pinned mirror by the finish launch */
+	uint32_t outbytes;
+};
+int   sgpu_bplan_rtcp_scatter(const uint8_t *arena, uint64_t arena_size,
+			      const struct sgpu_bplan_rtcp *r, void *stream);
+int   sgpu_bplan_rtcp_plan(const struct sgpu_bplan_rtcp *r, void *stream);
+int   sgpu_bplan_rtcp_finish(const struct sgpu_bplan_rtcp *r, void *stream);
+
 int   sgpu_plan_rtcp(const struct sgpu_rplan_in *in,
 		     const struct sgpu_hdr *hdr, const uint32_t *eix,
 		     const uint32_t *pos, const uint32_t *end,
