@@ -288,7 +288,10 @@ int srtp_alloc_many(struct srtp **srtpv, size_t n, enum srtp_suite suite,
  * plan was rejected for reordered or replayed packets goes straight to the
  * host engine, not to the device receive planner), "nomrplan" (an SRTCP
  * batch over many sessions on device windows goes through the host engine,
- * not the many-session SRTCP planner),
+ * not the many-session SRTCP planner), "nomsplan" (an RTP batch over many
+ * sessions on device windows whose sessions hold, or gain in the batch,
+ * several SSRCs goes through the host engine, not the many-session
+ * multi-SSRC planner),
  * "rxseq" (srtp_rx_index* and srtp_rx_fold walk
  * in one sequential pass, not in parallel parts), "freshmulti" (the
  * planner's first-batch hint: 1 sends a session's first batch to the
@@ -317,8 +320,11 @@ int srtp_gpu_tune(const char *name, long value);
  * "mrxplans" (reordered / duplicated many-session unprotect batches
  * completed by the bucket receive planner; "rxlate" and "rxdups" count its
  * packets too), "mrplans" (SRTCP batches over many sessions planned on the
- * device; srtp_gpu_tune "nomrplan" sends them through the host engine).  0
- * for an unknown name.
+ * device; srtp_gpu_tune "nomrplan" sends them through the host engine),
+ * "msplans" (RTP batches over many sessions with up to 8 SSRCs each, every
+ * stream in order, planned on the device; "mplans" does not count them, and
+ * "rejects" moves at most once per call; srtp_gpu_tune "nomsplan" sends them
+ * through the host engine).  0 for an unknown name.
  */
 uint64_t srtp_gpu_counter(const char *name);
 

@@ -360,6 +360,7 @@ static int run_dev(int op, struct srtp **sessv, size_t nsess,
 		   struct srtp_batch_dev *d)
 {
 	size_t k;
+	uint32_t mpf = 0;       /* why the bucket planner left a batch */
 	if (!sessv || !nsess || !d || !d->arena || !d->pos || !d->end ||
 	    !d->cap || !d->err)
 		return EINVAL;
@@ -381,11 +382,21 @@ static int run_dev(int op, struct srtp **sessv, size_t nsess,
 			r = dev_mrxplanned(sessv, nsess, d);
 		if (r >= 0)
 			return r;
+		if (r == -1)
+			mpf = pf;
 	}
 	{
 		int err = sess_host(sessv, nsess);
 		if (err)
 			return err;
+	}
+	/* sessions that hold, or gain in this batch, several SSRCs, each
+	 * stream in order: the multi-SSRC bucket planner over the host's
+	 * stream tables (current after sess_host) */
+	if (mpf && ms_eligible(op, nsess, mpf)) {
+		int r = dev_msplanned(op, sessv, nsess, d, mpf != MPF_MULTI);
+		if (r >= 0)
+			return r;
 	}
 	if ((op == OP_RTP_ENC || op == OP_RTP_DEC) && nsess == 1 &&
 	    !d->sess && !g_env.noplan && !g_env.general) {

@@ -617,8 +617,10 @@ static inline int dev_call(int op, struct srtp **sessv, size_t nsess,
 		err = timed ? sync_wait(&k, d->stream)
 			    : sgpu_stream_sync(d->stream);
 	t2 = timed ? mono_ns() : 0;
-	if (err)
+	if (err) {
+		*pfail = k.pfail;       /* -1 from the issue: why (MPF_MULTI) */
 		return err;
+	}
 	err = finish(&k);
 	if (timed) {
 		count(&g_cnt_sync_calls, 1);
@@ -1636,10 +1638,13 @@ static int dev_bplanned_issue(struct dcall *k, uint32_t bshift, uint32_t nb,
 	up_d = (struct sgpu_sstate *)w->ms.d;
 	need_d = (uint8_t *)(up_d + nsess);
 	k->t[0] = times ? now_ms() : 0;
-	if (mplan_gather_res(sessv, nsess, up_h, cm_h, need_h, &k->nup,
-			     k->pend, k->done)) {
+	err = mplan_gather_res(sessv, nsess, up_h, cm_h, need_h, &k->nup,
+			       k->pend, k->done);
+	if (err) {
 		/* the scatter only wrote scratch -- and the bucket counters,
 		 * zeroed again before the workspace's next call */
+		if (err == -2)
+			k->pfail = MPF_MULTI;
 		w->bp_d = NULL;
 		err = sgpu_stream_sync(stream);
 		return err ? err : -1;
@@ -1821,9 +1826,12 @@ int dev_mplanned_issue(struct dcall *k)
 	/* one pass over the sessions: suite check, slot map, and the states
 	 * the device does not hold yet (none once sessions are resident) */
 	k->t[0] = times ? now_ms() : 0;
-	if (mplan_gather_res(sessv, nsess, up_h, cm_h, need_h, &k->nup,
-			     k->pend, k->done)) {
+	err = mplan_gather_res(sessv, nsess, up_h, cm_h, need_h, &k->nup,
+			       k->pend, k->done);
+	if (err) {
 		/* the queued sort only wrote scratch */
+		if (err == -2)
+			k->pfail = MPF_MULTI;
 		err = sgpu_stream_sync(stream);
 		return err ? err : -1;
 	}
@@ -2184,5 +2192,207 @@ int dev_mrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 	count(&g_cnt_mrxplans, 1);
 	count(&g_cnt_rxlate, ro->nlate);
 	count(&g_cnt_rxdups, ro->ndup);
+	return 0;
+}
+
+/* ---- many sessions with up to 8 SSRCs each, in order ------------------- */
+
+/* a many-session RTP batch the bucket planner left for the planner of
+ * plan_buckets_rtp_streams.hip: its gather met a session that holds several
+ * streams (MPF_MULTI: no plan was tried), or its plan came back rejected for
+ * a second SSRC inside some session -- beside which a rejection for the
+ * order or a replayed index may only be that of two streams read as one */
+int ms_eligible(int op, size_t nsess, uint32_t pfail)
+{
+	if ((op != OP_RTP_ENC && op != OP_RTP_DEC) || nsess < 2 ||
+	    g_env.nomsplan)
+		return 0;
+	if (pfail == MPF_MULTI)
+		return 1;
+	return (pfail & SPF_SSRC) &&
+	       !(pfail & ~(uint32_t)(SPF_SSRC | SPF_ORDER | SPF_REPLAY));
+}
+
+/*
+ * Such a batch, every array in HBM, planned against the host's stream
+ * tables (current: run_dev called sess_host; the tables of sessions with
+ * several streams are not resident).  One pass over the sessions gathers the
+ * tables (msplan_gather), one upload, the bucket scatter (again: a rejected
+ * bucket plan's finish zeroed its counters), sgpu_bplan_rtps_plan, the
+ * general descriptor-driven crypto kernels with per-packet keys guarded by
+ * the plan, sgpu_bplan_rtps_finish, one copy back of the touched tables, one
+ * synchronisation, the apply.  counted: a plan of this call was counted as
+ * rejected already (rejects moves at most once per call).
+ * 0: done; -1: a batch the geometry or the gather does not take (nothing
+ * counted), a rejected plan, or a forged packet (undone) -- nothing
+ * modified, the caller's fallback continues; errno.
+ *
+ * w->ms: cm | toff | recs (up); w->mscr: sinfo | sout (down); w->bp: as
+ * dev_bplanned_issue lays it out as far as the scatter uses it (BP_HEAD, zero
+ * between calls | bucket entries | fail words); w->pl: plan out | fold out
+ * (the scatter zeroes its fail word; not used).
+ */
+int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
+		  struct srtp_batch_dev *d, int counted)
+{
+	const int prot = op == OP_RTP_ENC;
+	const struct comp *c0 = &sessv[0]->rtp;
+	const int gcm = c0->mode == SGPU_MODE_GCM;
+	const uint32_t T = gcm ? 16u : c0->tag_len;
+	const size_t n = d->n;
+	const size_t na = (n + SGPU_BP_BLOCK * SGPU_BP_PPT - 1) /
+			  (SGPU_BP_BLOCK * SGPU_BP_PPT);
+	const size_t o_toff = al256(nsess * 4);
+	const size_t o_recs = o_toff + al256((nsess + 1) * 4);
+	const size_t o_sout = al256(nsess * 4);
+	const size_t down = o_sout +
+			    nsess * SRTP_MAX_STREAMS * sizeof(struct sgpu_rtp_rec);
+	const size_t foff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
+		.vs = n * 5 + 64, .cm = 4, .pl = foff + 64, .es = n * 4};
+	struct ws_layout L;
+	struct sgpu_bplan_rtps R;
+	struct sgpu_bplan *B = &R.b;
+	struct sgpu_compact C;
+	struct sgpu_plan_out *po, *po_d;
+	uint32_t *toff_h, bshift, nb, cap;
+	size_t up;
+	void *stream = d->stream;
+	struct ws *w;
+	const int times = g_env.times;
+	double t[4];
+	int err;
+
+	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
+		return -1;
+	w = ws_get();
+	if (!w)
+		return ENOMEM;
+	err = ws_layout_reserve(w, n, &z, &L);
+	if (!err)
+		err = pool_reserve(w, &w->ms, o_recs + nsess * SRTP_MAX_STREAMS *
+				   sizeof(struct sgpu_rtp_rec));
+	if (!err)
+		err = pool_reserve(w, &w->mscr, down);
+	if (!err)
+		err = pool_reserve(w, &w->bp, BP_HEAD +
+				   al256((size_t)nb * cap * 16) + al256(na * 4));
+	if (err)
+		return err;
+	toff_h = (uint32_t *)(w->ms.h + o_toff);
+	t[0] = times ? now_ms() : 0;
+	if (msplan_gather(sessv, nsess, toff_h,
+			  (struct sgpu_rtp_rec *)(w->ms.h + o_recs),
+			  (uint32_t *)w->ms.h))
+		return -1;
+	up = o_recs + (size_t)toff_h[nsess] * sizeof(struct sgpu_rtp_rec);
+	t[1] = times ? now_ms() : 0;
+	if (w->bp_d != w->bp.d) {
+		/* a new pool (or a call that did not finish): counters from
+		 * zero */
+		err = sgpu_memset(w->bp.d, 0, BP_HEAD, stream);
+		if (err)
+			return err;
+		w->bp_d = w->bp.d;
+	}
+	po = (struct sgpu_plan_out *)w->pl.h;
+	po_d = (struct sgpu_plan_out *)w->pl.d;
+	memset(&R, 0, sizeof(R));
+	B->n = (uint32_t)n;
+	B->nsess = (uint32_t)nsess;
+	B->prot = (uint32_t)prot;
+	B->tag = T;
+	B->need = prot ? (gcm ? 16u : (T > 4 ? T : 4u)) : 0u;
+	B->maxlen = SGPU_CACHED_MAX(c0->mode);
+	B->bshift = bshift;
+	B->nb = nb;
+	B->cap = cap;
+	B->delta = prot ? (int32_t)T : -(int32_t)T;
+	B->gcm = (uint32_t)gcm;
+	B->pos = d->pos;
+	B->end = d->end;
+	B->capv = d->cap;
+	B->sess = d->sess;
+	B->posw = d->pos;
+	B->endw = d->end;
+	B->err = d->err;
+	B->es = L.es;
+	B->hdr = L.hdr;
+	B->desc = L.desc;
+	B->ticket = (uint32_t *)w->bp.d;
+	B->obins = (uint32_t *)(w->bp.d + 64);
+	B->bcount = (uint32_t *)(w->bp.d + 512);
+	B->tmp = (void *)(w->bp.d + BP_HEAD);
+	B->afail = (uint32_t *)(w->bp.d + BP_HEAD + al256((size_t)nb * cap * 16));
+	B->cm = (const uint32_t *)w->ms.d;
+	B->out = po_d;
+	B->fo = (struct sgpu_fold_out *)(w->pl.d + foff);
+	B->nfail = L.nfail;
+	B->outbytes = (uint32_t)offsetof(struct sgpu_plan_out, tail_ix);
+	B->outh = g_env.nopost ? NULL : (uint32_t *)po;
+	R.toff = (const uint32_t *)(w->ms.d + o_toff);
+	R.recs = (const struct sgpu_rtp_rec *)(w->ms.d + o_recs);
+	R.sinfo = (uint32_t *)w->mscr.d;
+	R.sout = (struct sgpu_rtp_rec *)(w->mscr.d + o_sout);
+	srv_stop(w);
+	err = sgpu_memcpy_h2d(w->ms.d, w->ms.h, up, stream);
+	if (!err)
+		err = sgpu_bplan_scatter(d->arena, d->arena_size, B, stream);
+	if (!err)
+		err = sgpu_bplan_rtps_plan(&R, stream);
+	/* the general kernels with per-packet session keys, array order:
+	 * AES-CM picks the header class from skip[], GCM has one */
+	C = compact_of(d, &L);
+	C.compmap = (const uint32_t *)w->ms.d;
+	C.sess = d->sess;
+	C.guard = gcm ? &po_d->fail : po_d->skip;
+	if (!err)
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, gcm ? 0 : -1, prot, stream);
+	if (!err)
+		err = sgpu_bplan_rtps_finish(&R, stream);
+	if (!err && g_env.nopost)
+		err = sgpu_memcpy_d2h(po, po_d, B->outbytes, stream);
+	if (!err)
+		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, down, stream);
+	t[2] = times ? now_ms() : 0;
+	if (!err)
+		err = sgpu_stream_sync(stream);
+	t[3] = times ? now_ms() : 0;
+	if (err) {
+		sgpu_stream_sync(stream);       /* no copy still reads ms.h */
+		w->bp_d = NULL;
+		return err;
+	}
+	if (po->fail) {
+		/* the crypto launch and the results did nothing */
+		if (!counted)
+			count(&g_cnt_rejects, 1);
+		if (g_env.times)
+			fprintf(stderr, "re_srtp msplan n=%zu nsess=%zu %s: "
+				"rejected (SPF %#x)\n", n, nsess,
+				prot ? "protect" : "unprotect", po->fail);
+		return -1;
+	}
+	if (po->nfail) {
+		/* a forged packet: undo on the device (no result was written,
+		 * the host's tables are as they were), fold on the host engine */
+		count(&g_cnt_misses, po->nfail);
+		count(&g_cnt_folds, 1);
+		C.undo = 1;
+		err = run_classes(d->arena, d->arena_size, C, c0, po_d, 0, stream);
+		if (!err)
+			err = sgpu_stream_sync(stream);
+		return err ? err : -1;
+	}
+	count(&g_cnt_msplans, 1);
+	msplan_apply(sessv, nsess, prot, (const uint32_t *)w->mscr.h,
+		     (const struct sgpu_rtp_rec *)(w->mscr.h + o_sout));
+	if (times)
+		fprintf(stderr, "re_srtp msplan n=%zu nsess=%zu %s: gather "
+			"%.3f submit %.3f wait %.3f apply %.3f ms\n", n, nsess,
+			prot ? "protect" : "unprotect", t[1] - t[0], t[2] - t[1],
+			t[3] - t[2], now_ms() - t[3]);
 	return 0;
 }

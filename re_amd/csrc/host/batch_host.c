@@ -584,6 +584,8 @@ struct mpg {
 	const struct tk_owner *own;     /* ... and the issuing thread */
 };
 
+enum { MPG_BAD = 1, MPG_MULTI = 2 };    /* struct mpg bad */
+
 static void mplan_gather_part(void *arg, size_t a, size_t b)
 {
 	struct mpg *g = arg;
@@ -593,8 +595,14 @@ static void mplan_gather_part(void *arg, size_t a, size_t b)
 		struct sgpu_sstate *st = &g->st[k];
 		if (k + 16 < b)
 			__builtin_prefetch(g->sessv[k + 16], 0, 1);
-		if (s->nstreams > 1 || s->suite != g->suite) {
-			atomic_store(&g->bad, 1);
+		if (s->nstreams > 1) {
+			/* several streams: not this planner's, and no plan was
+			 * tried (MPG_MULTI: dev_msplanned may take the batch) */
+			atomic_fetch_or(&g->bad, MPG_MULTI);
+			return;
+		}
+		if (s->suite != g->suite) {
+			atomic_fetch_or(&g->bad, MPG_BAD);
 			return;
 		}
 		/* two sessv entries naming one context would plan the same
@@ -602,7 +610,7 @@ static void mplan_gather_part(void *arg, size_t a, size_t b)
 		 * host engines work through the pointers) */
 		if (__atomic_exchange_n(&((struct srtp *)s)->mp_epoch, g->epoch,
 					__ATOMIC_RELAXED) == g->epoch) {
-			atomic_store(&g->bad, 1);
+			atomic_fetch_or(&g->bad, MPG_BAD);
 			return;
 		}
 		if (g->cm)
@@ -610,14 +618,14 @@ static void mplan_gather_part(void *arg, size_t a, size_t b)
 		/* another thread's pending call: not plannable here (the
 		 * host paths behind a rejected plan return EBUSY) */
 		if (s->pend_own && s->pend_own != g->own && sess_busy(s)) {
-			atomic_store(&g->bad, 1);
+			atomic_fetch_or(&g->bad, MPG_BAD);
 			return;
 		}
 		if (g->pend) {
 			/* a pending single-stream call plans from host state
 			 * this call cannot see yet */
 			if (s->pend_own == g->own && s->pend_p > g->done) {
-				atomic_store(&g->bad, 1);
+				atomic_fetch_or(&g->bad, MPG_BAD);
 				return;
 			}
 			((struct srtp *)s)->pend_m = g->pend;
@@ -667,7 +675,8 @@ static int mplan_gather(struct srtp **sessv, size_t nsess,
  * current are only mapped (and marked DRES_DEV); host-newer ones are
  * copied to st[k] with need[k] = 1 for sgpu_sst_load.  *nup = how many.
  * -1: not plannable (the caller uploads nothing: need[] is ignored and
- * the marks are undone).
+ * the marks are undone); -2: the same, and the only thing in the way was a
+ * session that holds several streams.
  */
 int mplan_gather_res(struct srtp **sessv, size_t nsess,
 			    struct sgpu_sstate *st, uint32_t *cm,
@@ -685,7 +694,7 @@ int mplan_gather_res(struct srtp **sessv, size_t nsess,
 	if (atomic_load(&g.bad)) {
 		/* the device copies of sessions marked DEV here were current
 		 * already (DRES_BOTH or DRES_DEV): DEV is still true */
-		return -1;
+		return atomic_load(&g.bad) == MPG_MULTI ? -2 : -1;
 	}
 	if (*nup)
 		for (k = 0; k < nsess; k++)
@@ -840,6 +849,149 @@ void mrplan_apply(struct srtp **sessv, size_t nsess, int prot,
 	struct mrg g = {.sessv = sessv, .sinfo = sinfo, .sout = sout,
 			.prot = prot, .hmac = sessv[0]->rtcp.has_hmac};
 	par_for(nsess, mplan_par(), mrplan_apply_part, &g);
+}
+
+/* ---- many-session RTP device plan, up to 8 SSRCs each (dev_msplanned) -- */
+
+struct msg {
+	struct srtp **sessv;
+	uint32_t *toff, *cm;
+	struct sgpu_rtp_rec *recs;
+	const struct sgpu_rtp_rec *sout;
+	const uint32_t *sinfo;
+	int prot;
+	uint32_t epoch;
+	atomic_int bad;
+};
+
+/* pass 1: the sessions a plan can take, the slot map, the table sizes */
+static void msplan_count_part(void *arg, size_t a, size_t b)
+{
+	struct msg *g = arg;
+	const struct srtp *s0 = g->sessv[0];
+	size_t k;
+	for (k = a; k < b; k++) {
+		struct srtp *s = g->sessv[k];
+		if (k + 16 < b)
+			__builtin_prefetch(g->sessv[k + 16], 0, 1);
+		/* one suite: one kernel class, one tag length */
+		if (s->suite != s0->suite || s->nstreams > SRTP_MAX_STREAMS) {
+			atomic_store(&g->bad, 1);
+			return;
+		}
+		/* two sessv entries naming one context (mplan_gather_part) */
+		if (__atomic_exchange_n(&s->mp_epoch, g->epoch,
+					__ATOMIC_RELAXED) == g->epoch) {
+			atomic_store(&g->bad, 1);
+			return;
+		}
+		g->cm[k] = 2u * s->slot;                /* comp[0] = RTP */
+		g->toff[k + 1] = s->nstreams;
+	}
+}
+
+/* pass 2: the stream records behind their offsets */
+static void msplan_fill_part(void *arg, size_t a, size_t b)
+{
+	struct msg *g = arg;
+	size_t k;
+	for (k = a; k < b; k++) {
+		const struct srtp *s = g->sessv[k];
+		struct sgpu_rtp_rec *r = g->recs + g->toff[k];
+		unsigned i;
+		if (k + 16 < b)
+			__builtin_prefetch(g->sessv[k + 16], 0, 1);
+		for (i = 0; i < s->nstreams; i++) {
+			const struct srtp_stream *x = &s->streams[i];
+			r[i].ssrc = x->ssrc;
+			r[i].roc = x->roc;
+			r[i].sl = x->s_l | (x->s_l_set ? 0x10000u : 0u);
+			r[i].pad = 0;
+			r[i].llo = (uint32_t)x->replay_rtp.lix;
+			r[i].lhi = (uint32_t)(x->replay_rtp.lix >> 32);
+			r[i].blo = (uint32_t)x->replay_rtp.bitmap;
+			r[i].bhi = (uint32_t)(x->replay_rtp.bitmap >> 32);
+		}
+	}
+}
+
+/*
+ * The sessions' stream tables for the many-session multi-SSRC RTP planner:
+ * toff (nsess + 1 offsets), recs (the streams in table order, at most 8 per
+ * session), cm (session -> RTP component).  The host's tables are current
+ * (run_dev called sess_host, which also answers EBUSY for a session with a
+ * pending call).  -1: not a batch it takes (sessions of different suites,
+ * one context named twice); nothing is modified either way.
+ */
+int msplan_gather(struct srtp **sessv, size_t nsess, uint32_t *toff,
+		  struct sgpu_rtp_rec *recs, uint32_t *cm)
+{
+	struct msg g = {.sessv = sessv, .toff = toff, .cm = cm, .recs = recs};
+	size_t k;
+	do {
+		g.epoch = __atomic_add_fetch(&g_epoch, 1, __ATOMIC_RELAXED);
+	} while (!g.epoch);
+	toff[0] = 0;
+	par_for(nsess, mplan_par(), msplan_count_part, &g);
+	if (atomic_load(&g.bad))
+		return -1;
+	for (k = 0; k < nsess; k++)
+		toff[k + 1] += toff[k];
+	par_for(nsess, mplan_par(), msplan_fill_part, &g);
+	return 0;
+}
+
+static void msplan_apply_part(void *arg, size_t a, size_t b)
+{
+	struct msg *g = arg;
+	size_t k;
+	for (k = a; k < b; k++) {
+		const uint32_t si = g->sinfo[k];
+		const uint32_t nst = si & 0xffu, mask = si >> 8 & 0xffu;
+		const struct sgpu_rtp_rec *o = g->sout + k * SRTP_MAX_STREAMS;
+		struct srtp *s;
+		unsigned i;
+		if (k + 16 < b && g->sinfo[k + 16])
+			__builtin_prefetch(g->sessv[k + 16], 1, 1);
+		if (!si)
+			continue;
+		s = g->sessv[k];
+		for (i = 0; i < nst && i < SRTP_MAX_STREAMS; i++) {
+			struct srtp_stream *x = &s->streams[i];
+			if (i >= s->nstreams) {
+				/* stream_new (stream.c:45-67) */
+				memset(x, 0, sizeof(*x));
+				x->ssrc = o[i].ssrc;
+			}
+			if (!(mask >> i & 1u))
+				continue;
+			x->roc = o[i].roc;
+			x->s_l = (uint16_t)o[i].sl;
+			x->s_l_set = 1;
+			if (!g->prot) {
+				x->replay_rtp.lix = (uint64_t)o[i].lhi << 32 |
+						    o[i].llo;
+				x->replay_rtp.bitmap = (uint64_t)o[i].bhi << 32 |
+						       o[i].blo;
+			}
+		}
+		if (nst > s->nstreams)
+			s->nstreams = nst < SRTP_MAX_STREAMS ? nst
+							     : SRTP_MAX_STREAMS;
+		/* the host copy is the newer one: a later bucket-planner call
+		 * uploads it */
+		s->dres = DRES_HOST;
+	}
+}
+
+/* the touched sessions' tables after an accepted plan (sinfo, sout: pinned
+ * copies of the planner's) into the host's */
+void msplan_apply(struct srtp **sessv, size_t nsess, int prot,
+		  const uint32_t *sinfo, const struct sgpu_rtp_rec *sout)
+{
+	struct msg g = {.sessv = sessv, .sinfo = sinfo, .sout = sout,
+			.prot = prot};
+	par_for(nsess, mplan_par(), msplan_apply_part, &g);
 }
 
 static void mplan_apply_part(void *arg, size_t a, size_t b)

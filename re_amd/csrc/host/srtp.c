@@ -129,6 +129,9 @@ uint64_t g_cnt_mplans;   /* multi-session device plans accepted */
 uint64_t g_cnt_rplans;   /* SRTCP device plans (k_plan_rtcp) accepted */
 uint64_t g_cnt_mrplans;  /* many-session SRTCP device plans
 				   (plan_buckets_rtcp.hip) accepted */
+uint64_t g_cnt_msplans;  /* many-session RTP device plans over sessions of
+				   several SSRCs (plan_buckets_rtp_streams.hip)
+				   accepted */
 uint64_t g_cnt_lplans;   /* single-stream batches planned by the
 				   one-launch planner (k_lp_plan), accepted */
 uint64_t g_cnt_rxplans;  /* reordered / duplicated one-stream unprotect
@@ -212,6 +215,8 @@ uint64_t srtp_gpu_counter(const char *name)
 		return __atomic_load_n(&g_cnt_rplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "mrplans"))
 		return __atomic_load_n(&g_cnt_mrplans, __ATOMIC_RELAXED);
+	if (!strcmp(name, "msplans"))
+		return __atomic_load_n(&g_cnt_msplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "lbtimeouts"))
 		return __atomic_load_n(&g_cnt_lbtimeout, __ATOMIC_RELAXED);
 	if (!strcmp(name, "pcbatches"))
@@ -309,6 +314,8 @@ int srtp_gpu_tune(const char *name, long value)
 		g_env.norxplan = value > 0;
 	else if (!strcmp(name, "nomrplan"))
 		g_env.nomrplan = value > 0;
+	else if (!strcmp(name, "nomsplan"))
+		g_env.nomsplan = value > 0;
 	else if (!strcmp(name, "rxseq"))
 		g_env.rxseq = value > 0;
 	else if (!strcmp(name, "freshmulti"))

@@ -127,6 +127,11 @@ struct srtp_env {
 				   the receive planner (one stream:
 				   plan_rx.hip; many sessions:
 				   plan_buckets_rx.hip) */
+	int nomsplan;           /* srtp_gpu_tune nomsplan: many-session RTP
+				   batches on device windows whose sessions
+				   hold several SSRCs go through the host
+				   engine (dev_staged), not the planner of
+				   plan_buckets_rtp_streams.hip */
 	int nomrplan;           /* srtp_gpu_tune nomrplan: many-session SRTCP
 				   batches on device windows go through the
 				   host engine (dev_staged), not the bucket
@@ -288,7 +293,7 @@ extern uint64_t g_cnt_pcbatch, g_cnt_pcpkts, g_cnt_pcfused, g_cnt_rxw_redo;
 extern uint64_t g_cnt_misses, g_cnt_folds, g_cnt_rejects, g_cnt_devfolds;
 extern uint64_t g_cnt_splans, g_cnt_fused, g_cnt_gated;
 extern uint64_t g_cnt_dplans, g_cnt_mplans, g_cnt_rplans, g_cnt_lbtimeout;
-extern uint64_t g_cnt_lplans, g_cnt_mrplans;
+extern uint64_t g_cnt_lplans, g_cnt_mrplans, g_cnt_msplans;
 extern uint64_t g_cnt_rxplans, g_cnt_rxlate, g_cnt_rxdups, g_cnt_mrxplans;
 extern int g_fresh_multi;       /* srtp.c: the last first batch of a session
 				   showed several SSRCs (see there) */
@@ -484,6 +489,10 @@ int mrplan_gather(struct srtp **sessv, size_t nsess, int prot, uint32_t *toff,
 		  struct sgpu_rtcp_rec *recs, uint32_t *cm);
 void mrplan_apply(struct srtp **sessv, size_t nsess, int prot,
 		  const uint32_t *sinfo, const struct sgpu_rtcp_rec *sout);
+int msplan_gather(struct srtp **sessv, size_t nsess, uint32_t *toff,
+		  struct sgpu_rtp_rec *recs, uint32_t *cm);
+void msplan_apply(struct srtp **sessv, size_t nsess, int prot,
+		  const uint32_t *sinfo, const struct sgpu_rtp_rec *sout);
 int run_classes(uint8_t *arena, uint64_t asz, struct sgpu_compact C,
 		       const struct comp *c0, struct sgpu_plan_out *po_d,
 		       int prot, void *stream);
@@ -511,6 +520,12 @@ int dev_mplanned_(int op, struct srtp **sessv, size_t nsess,
 int dev_mplanned(int op, struct srtp **sessv, size_t nsess,
 			struct srtp_batch_dev *d, uint32_t *pfail);
 int mrx_eligible(int op, size_t nsess, uint32_t pfail);
+/* dev_mplanned's *pfail beside the plan's SPF_* bits: no plan was tried, the
+ * gather met a session that holds several streams (dev_msplanned's) */
+#define MPF_MULTI 0x80000000u
+int ms_eligible(int op, size_t nsess, uint32_t pfail);
+int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
+		  struct srtp_batch_dev *d, int counted);
 int dev_mrxplanned(struct srtp **sessv, size_t nsess,
 		   struct srtp_batch_dev *d);
 

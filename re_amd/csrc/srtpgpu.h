@@ -861,6 +861,56 @@ int   sgpu_bplan_rtcp_scatter(const uint8_t *arena, uint64_t arena_size,
 int   sgpu_bplan_rtcp_plan(const struct sgpu_bplan_rtcp *r, void *stream);
 int   sgpu_bplan_rtcp_finish(const struct sgpu_bplan_rtcp *r, void *stream);
 
+/*
+ * RTP batches over many sessions with up to 8 SSRCs each, in order per
+ * stream, planned on the device behind the bucket planner
+ * (plan_buckets_rtp_streams.hip; the rule per (session, SSRC):
+ * hip/plan_rtp_seg.h), with the bucket geometry of sgpu_bplan_geometry:
+ *   sgpu_bplan_scatter      again, unchanged (b: pred / gate / flist NULL; it
+ *                           zeroes out->fail and *nfail, opens packet 0's
+ *                           class guard and makes the window and header
+ *                           checks)
+ *   sgpu_bplan_rtps_plan    per bucket (one workgroup, in LDS): the sessions'
+ *                           stream tables (toff / recs), the entries grouped
+ *                           by session and ranked by packet index, per packet
+ *                           the look back over its session's segment (slot as
+ *                           for SRTCP; the stream's packet before it, its
+ *                           rollovers so far), the rule, desc, the window
+ *                           bits, each touched session's table after the
+ *                           batch (sout, sinfo); a failed check: out->fail |=,
+ *                           out->skip[0..3] = 1
+ *   (the general crypto kernels over every packet in array order with
+ *   per-packet keys through sess and cm, guarded by out->skip[] -- GCM:
+ *   out->fail -- counting their tag misses in *nfail)
+ *   sgpu_bplan_rtps_finish  if !out->fail and !*nfail: end / err per packet;
+ *                           always: bcount / obins back to zero, out->nfail,
+ *                           and outbytes from out to outh
+ * out->fail or out->nfail after it: nothing of the caller's was modified but
+ * the packets the crypto launches processed (undo: the same kernels,
+ * sgpu_compact undo).  b->order, sorted, sseg, ticket, sst, up, upneed, sout,
+ * verdict are not used.
+ */
+struct sgpu_rtp_rec {           /* hip/plan_rtp_seg.h struct tseg_rec */
+	uint32_t ssrc, roc;
+	uint32_t sl;            /* s_l | s_l_set << 16 */
+	uint32_t pad;
+	uint32_t llo, lhi;      /* replay_rtp.lix */
+	uint32_t blo, bhi;      /* replay_rtp.bitmap */
+};
+
+struct sgpu_bplan_rtps {
+	struct sgpu_bplan b;
+	const uint32_t *toff;           /* nsess + 1: session s's streams are
+					   recs[toff[s] .. toff[s + 1]) */
+	const struct sgpu_rtp_rec *recs;
+	struct sgpu_rtp_rec *sout;      /* nsess x 8: the tables after */
+	uint32_t *sinfo;                /* nsess: streams after the batch |
+					   the touched streams' bits << 8
+					   (0: the session had no packet) */
+};
+int   sgpu_bplan_rtps_plan(const struct sgpu_bplan_rtps *r, void *stream);
+int   sgpu_bplan_rtps_finish(const struct sgpu_bplan_rtps *r, void *stream);
+
 int   sgpu_plan_rtcp(const struct sgpu_rplan_in *in,
 		     const struct sgpu_hdr *hdr, const uint32_t *eix,
 		     const uint32_t *pos, const uint32_t *end,
