@@ -291,7 +291,9 @@ int srtp_alloc_many(struct srtp **srtpv, size_t n, enum srtp_suite suite,
  * not the many-session SRTCP planner), "nomsplan" (an RTP batch over many
  * sessions on device windows whose sessions hold, or gain in the batch,
  * several SSRCs goes through the host engine, not the many-session
- * multi-SSRC planner),
+ * multi-SSRC planner), "nomsrxplan" (such an unprotect batch whose plan was
+ * rejected for reordered or replayed packets inside some stream goes
+ * straight to the host engine, not to the multi-SSRC receive planner),
  * "rxseq" (srtp_rx_index* and srtp_rx_fold walk
  * in one sequential pass, not in parallel parts), "freshmulti" (the
  * planner's first-batch hint: 1 sends a session's first batch to the
@@ -324,7 +326,12 @@ int srtp_gpu_tune(const char *name, long value);
  * "msplans" (RTP batches over many sessions with up to 8 SSRCs each, every
  * stream in order, planned on the device; "mplans" does not count them, and
  * "rejects" moves at most once per call; srtp_gpu_tune "nomsplan" sends them
- * through the host engine).  0 for an unknown name.
+ * through the host engine), "msrxplans" (unprotect batches over such
+ * sessions whose streams arrived reordered, with gaps, duplicated or
+ * replayed, completed by the multi-SSRC receive planner behind a rejected
+ * in-order plan; "rxlate" and "rxdups" count its packets too, "msplans",
+ * "mplans" and "mrxplans" do not move for them; srtp_gpu_tune "nomsrxplan"
+ * sends them through the host engine).  0 for an unknown name.
  */
 uint64_t srtp_gpu_counter(const char *name);
 

@@ -394,7 +394,12 @@ static int run_dev(int op, struct srtp **sessv, size_t nsess,
 	 * stream in order: the multi-SSRC bucket planner over the host's
 	 * stream tables (current after sess_host) */
 	if (mpf && ms_eligible(op, nsess, mpf)) {
-		int r = dev_msplanned(op, sessv, nsess, d, mpf != MPF_MULTI);
+		uint32_t pf = 0;
+		int r = dev_msplanned(op, sessv, nsess, d, mpf != MPF_MULTI, &pf);
+		/* reordered or replayed arrivals inside some stream: the receive
+		 * planner on the tables that plan uploaded */
+		if (r == -1 && msrx_eligible(op, pf))
+			r = dev_msrxplanned(sessv, nsess, d);
 		if (r >= 0)
 			return r;
 	}

@@ -9,7 +9,10 @@
  * (dev_planned_rtcp; many sessions with up to 8 SSRCs each:
  * plan_buckets_rtcp.hip, dev_mplanned_rtcp), many sessions with resident
  * state (dev_mplanned) and their reordered arrivals (plan_buckets_rx.hip,
- * dev_mrxplanned).  Each call is a struct dcall between its launches
+ * dev_mrxplanned), many sessions with up to 8 SSRCs each
+ * (plan_buckets_rtp_streams.hip, dev_msplanned) and their reordered
+ * arrivals (plan_buckets_rtp_streams_rx.hip, dev_msrxplanned).  Each call
+ * of the others is a struct dcall between its launches
  * (*_issue) and its completion (*_finish), so the synchronous calls
  * (dev_call) and the asynchronous tickets (batch_async.c) share it.  Where a
  * call's arrays lie in the workspace pools: struct ws_layout (srtp_int.h)
@@ -2222,7 +2225,8 @@ int ms_eligible(int op, size_t nsess, uint32_t pfail)
  * general descriptor-driven crypto kernels with per-packet keys guarded by
  * the plan, sgpu_bplan_rtps_finish, one copy back of the touched tables, one
  * synchronisation, the apply.  counted: a plan of this call was counted as
- * rejected already (rejects moves at most once per call).
+ * rejected already (rejects moves at most once per call); *pfail: a rejected
+ * plan's SPF_* bits (0 otherwise).
  * 0: done; -1: a batch the geometry or the gather does not take (nothing
  * counted), a rejected plan, or a forged packet (undone) -- nothing
  * modified, the caller's fallback continues; errno.
@@ -2233,7 +2237,7 @@ int ms_eligible(int op, size_t nsess, uint32_t pfail)
  * (the scatter zeroes its fail word; not used).
  */
 int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
-		  struct srtp_batch_dev *d, int counted)
+		  struct srtp_batch_dev *d, int counted, uint32_t *pfail)
 {
 	const int prot = op == OP_RTP_ENC;
 	const struct comp *c0 = &sessv[0]->rtp;
@@ -2264,6 +2268,7 @@ int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
 	double t[4];
 	int err;
 
+	*pfail = 0;
 	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
 		return -1;
 	w = ws_get();
@@ -2373,6 +2378,7 @@ int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
 			fprintf(stderr, "re_srtp msplan n=%zu nsess=%zu %s: "
 				"rejected (SPF %#x)\n", n, nsess,
 				prot ? "protect" : "unprotect", po->fail);
+		*pfail = po->fail;
 		return -1;
 	}
 	if (po->nfail) {
@@ -2394,5 +2400,183 @@ int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
 			"%.3f submit %.3f wait %.3f apply %.3f ms\n", n, nsess,
 			prot ? "protect" : "unprotect", t[1] - t[0], t[2] - t[1],
 			t[3] - t[2], now_ms() - t[3]);
+	return 0;
+}
+
+/* ---- many sessions with up to 8 SSRCs each, reordered arrivals --------- */
+
+/* a rejected plan of dev_msplanned the receive planner
+ * (plan_buckets_rtp_streams_rx.hip) may settle: only the arrival order or a
+ * replayed index inside some stream was in its way */
+int msrx_eligible(int op, uint32_t pfail)
+{
+	return op == OP_RTP_DEC && !g_env.nomsplan && !g_env.nomsrxplan &&
+	       pfail && !(pfail & ~(uint32_t)(SPF_ORDER | SPF_REPLAY));
+}
+
+/*
+ * A many-session unprotect batch behind such a rejection, on this thread's
+ * workspace as dev_msplanned left it: the rejected plan modified nothing, so
+ * its upload (w->ms.d: cm | toff | recs) is still the truth and nothing is
+ * gathered or uploaded again.  The bucket scatter again (the rejected plan's
+ * finish zeroed its counters), sgpu_bplan_rtps_rx_plan, the general
+ * descriptor-driven crypto kernels in array order with per-packet keys
+ * guarded by its verdict, sgpu_bplan_rtps_rx_finish, one copy back of the
+ * touched tables, one synchronisation, the apply (msplan_apply).
+ * 0: done; -1: not settled, or a forged packet (undone) -- nothing modified,
+ * the caller's fallback continues; errno.
+ *
+ * w->ms, w->mscr as in dev_msplanned; w->bp: BP_HEAD | bucket entries | fail
+ * words | per-bucket counts | verdict bytes; w->pl: plan out | fold out
+ * (unused) | sgpu_bprx_out.
+ */
+int dev_msrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
+{
+	const struct comp *c0 = &sessv[0]->rtp;
+	const int gcm = c0->mode == SGPU_MODE_GCM;
+	const uint32_t T = gcm ? 16u : c0->tag_len;
+	const size_t n = d->n;
+	const size_t na = (n + SGPU_BP_BLOCK * SGPU_BP_PPT - 1) /
+			  (SGPU_BP_BLOCK * SGPU_BP_PPT);
+	const size_t o_toff = al256(nsess * 4);
+	const size_t o_recs = o_toff + al256((nsess + 1) * 4);
+	const size_t o_sout = al256(nsess * 4);
+	const size_t down = o_sout +
+			    nsess * SRTP_MAX_STREAMS * sizeof(struct sgpu_rtp_rec);
+	const size_t roff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
+		.vs = n * 5 + 64, .cm = 4, .pl = roff + 128, .es = n * 4};
+	struct ws_layout L;
+	struct sgpu_bplan_rtps_rx R;
+	struct sgpu_bplan *B = &R.s.b;
+	struct sgpu_compact C;
+	struct sgpu_plan_out *po, *po_d;
+	const struct sgpu_bprx_out *ro;
+	uint32_t bshift, nb, cap;
+	size_t o_afail, o_cnt, o_rs;
+	void *stream = d->stream;
+	struct ws *w;
+	int err;
+
+	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
+		return -1;
+	w = ws_get();
+	if (!w)
+		return ENOMEM;
+	/* the upload must be the one dev_msplanned made: never a new pool */
+	if (w->ms.cap < o_recs + nsess * SRTP_MAX_STREAMS *
+			 sizeof(struct sgpu_rtp_rec) || w->mscr.cap < down)
+		return -1;
+	o_afail = BP_HEAD + al256((size_t)nb * cap * 16);
+	o_cnt = o_afail + al256(na * 4);
+	o_rs = o_cnt + al256((size_t)nb * 8);
+	err = ws_layout_reserve(w, n, &z, &L);
+	if (!err)
+		err = pool_reserve(w, &w->bp, o_rs + al256(n));
+	if (err)
+		return err;
+	if (w->bp_d != w->bp.d) {
+		/* a new pool (or a call that did not finish): counters from
+		 * zero */
+		err = sgpu_memset(w->bp.d, 0, BP_HEAD, stream);
+		if (err)
+			return err;
+		w->bp_d = w->bp.d;
+	}
+	po = (struct sgpu_plan_out *)w->pl.h;
+	po_d = (struct sgpu_plan_out *)w->pl.d;
+	ro = (const struct sgpu_bprx_out *)(w->pl.h + roff + 64);
+	memset(&R, 0, sizeof(R));
+	B->n = (uint32_t)n;
+	B->nsess = (uint32_t)nsess;
+	B->tag = T;
+	B->maxlen = SGPU_CACHED_MAX(c0->mode);
+	B->bshift = bshift;
+	B->nb = nb;
+	B->cap = cap;
+	B->delta = -(int32_t)T;
+	B->gcm = (uint32_t)gcm;
+	B->pos = d->pos;
+	B->end = d->end;
+	B->capv = d->cap;
+	B->sess = d->sess;
+	B->posw = d->pos;
+	B->endw = d->end;
+	B->err = d->err;
+	B->es = L.es;
+	B->hdr = L.hdr;
+	B->desc = L.desc;
+	B->ticket = (uint32_t *)w->bp.d;
+	B->obins = (uint32_t *)(w->bp.d + 64);
+	B->bcount = (uint32_t *)(w->bp.d + 512);
+	B->tmp = (void *)(w->bp.d + BP_HEAD);
+	B->afail = (uint32_t *)(w->bp.d + o_afail);
+	B->cm = (const uint32_t *)w->ms.d;
+	B->out = po_d;
+	B->fo = (struct sgpu_fold_out *)(w->pl.d + roff);
+	B->nfail = L.nfail;
+	B->outbytes = (uint32_t)(roff + 64 + sizeof(struct sgpu_bprx_out));
+	B->outh = g_env.nopost ? NULL : (uint32_t *)po;
+	R.s.toff = (const uint32_t *)(w->ms.d + o_toff);
+	R.s.recs = (const struct sgpu_rtp_rec *)(w->ms.d + o_recs);
+	R.s.sinfo = (uint32_t *)w->mscr.d;
+	R.s.sout = (struct sgpu_rtp_rec *)(w->mscr.d + o_sout);
+	R.cnt = (uint32_t *)(w->bp.d + o_cnt);
+	R.rs = w->bp.d + o_rs;
+	R.ro = (struct sgpu_bprx_out *)(w->pl.d + roff + 64);
+	R.lookback = RX_LOOKBACK;
+	R.hmac = !gcm;
+	srv_stop(w);
+	err = sgpu_bplan_scatter(d->arena, d->arena_size, B, stream);
+	if (!err)
+		err = sgpu_bplan_rtps_rx_plan(&R, stream);
+	/* the general kernels (EALREADY packets: MAC only) with per-packet
+	 * session keys, array order: AES-CM picks the header class from
+	 * skip[], GCM has one */
+	C = compact_of(d, &L);
+	C.compmap = (const uint32_t *)w->ms.d;
+	C.sess = d->sess;
+	C.guard = gcm ? &po_d->fail : po_d->skip;
+	if (!err)
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, gcm ? 0 : -1, 0, stream);
+	if (!err)
+		err = sgpu_bplan_rtps_rx_finish(&R, stream);
+	if (!err && g_env.nopost)
+		err = sgpu_memcpy_d2h(po, po_d, B->outbytes, stream);
+	if (!err)
+		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, down, stream);
+	if (!err)
+		err = sgpu_stream_sync(stream);
+	if (err) {
+		sgpu_stream_sync(stream);
+		w->bp_d = NULL;
+		return err;
+	}
+	if (po->fail) {
+		/* the crypto launch and the results did nothing (the rejection
+		 * was counted: dev_msplanned's, or the bucket planner's) */
+		if (g_env.times)
+			fprintf(stderr, "re_srtp msrx plan n=%zu nsess=%zu: not "
+				"settled (SPF %#x)\n", n, nsess, po->fail);
+		return -1;
+	}
+	if (po->nfail) {
+		/* a forged packet: undo on the device (no result was written,
+		 * the host's tables are as they were), fold on the host engine */
+		count(&g_cnt_misses, po->nfail);
+		count(&g_cnt_folds, 1);
+		C.undo = 1;
+		err = run_classes(d->arena, d->arena_size, C, c0, po_d, 0, stream);
+		if (!err)
+			err = sgpu_stream_sync(stream);
+		return err ? err : -1;
+	}
+	count(&g_cnt_msrxplans, 1);
+	count(&g_cnt_rxlate, ro->nlate);
+	count(&g_cnt_rxdups, ro->ndup);
+	msplan_apply(sessv, nsess, 0, (const uint32_t *)w->mscr.h,
+		     (const struct sgpu_rtp_rec *)(w->mscr.h + o_sout));
 	return 0;
 }

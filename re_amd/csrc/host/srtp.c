@@ -132,6 +132,10 @@ uint64_t g_cnt_mrplans;  /* many-session SRTCP device plans
 uint64_t g_cnt_msplans;  /* many-session RTP device plans over sessions of
 				   several SSRCs (plan_buckets_rtp_streams.hip)
 				   accepted */
+uint64_t g_cnt_msrxplans; /* ... reordered / duplicated unprotect batches
+				   over such sessions completed by the receive
+				   planner (plan_buckets_rtp_streams_rx.hip);
+				   rxlate and rxdups count its packets too */
 uint64_t g_cnt_lplans;   /* single-stream batches planned by the
 				   one-launch planner (k_lp_plan), accepted */
 uint64_t g_cnt_rxplans;  /* reordered / duplicated one-stream unprotect
@@ -217,6 +221,8 @@ uint64_t srtp_gpu_counter(const char *name)
 		return __atomic_load_n(&g_cnt_mrplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "msplans"))
 		return __atomic_load_n(&g_cnt_msplans, __ATOMIC_RELAXED);
+	if (!strcmp(name, "msrxplans"))
+		return __atomic_load_n(&g_cnt_msrxplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "lbtimeouts"))
 		return __atomic_load_n(&g_cnt_lbtimeout, __ATOMIC_RELAXED);
 	if (!strcmp(name, "pcbatches"))
@@ -316,6 +322,8 @@ int srtp_gpu_tune(const char *name, long value)
 		g_env.nomrplan = value > 0;
 	else if (!strcmp(name, "nomsplan"))
 		g_env.nomsplan = value > 0;
+	else if (!strcmp(name, "nomsrxplan"))
+		g_env.nomsrxplan = value > 0;
 	else if (!strcmp(name, "rxseq"))
 		g_env.rxseq = value > 0;
 	else if (!strcmp(name, "freshmulti"))

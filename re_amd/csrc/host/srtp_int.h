@@ -132,6 +132,11 @@ struct srtp_env {
 				   hold several SSRCs go through the host
 				   engine (dev_staged), not the planner of
 				   plan_buckets_rtp_streams.hip */
+	int nomsrxplan;         /* srtp_gpu_tune nomsrxplan: such an unprotect
+				   batch whose plan was rejected for reordered
+				   or replayed packets goes straight to the
+				   host engine, not to the receive planner of
+				   plan_buckets_rtp_streams_rx.hip */
 	int nomrplan;           /* srtp_gpu_tune nomrplan: many-session SRTCP
 				   batches on device windows go through the
 				   host engine (dev_staged), not the bucket
@@ -293,7 +298,7 @@ extern uint64_t g_cnt_pcbatch, g_cnt_pcpkts, g_cnt_pcfused, g_cnt_rxw_redo;
 extern uint64_t g_cnt_misses, g_cnt_folds, g_cnt_rejects, g_cnt_devfolds;
 extern uint64_t g_cnt_splans, g_cnt_fused, g_cnt_gated;
 extern uint64_t g_cnt_dplans, g_cnt_mplans, g_cnt_rplans, g_cnt_lbtimeout;
-extern uint64_t g_cnt_lplans, g_cnt_mrplans, g_cnt_msplans;
+extern uint64_t g_cnt_lplans, g_cnt_mrplans, g_cnt_msplans, g_cnt_msrxplans;
 extern uint64_t g_cnt_rxplans, g_cnt_rxlate, g_cnt_rxdups, g_cnt_mrxplans;
 extern int g_fresh_multi;       /* srtp.c: the last first batch of a session
 				   showed several SSRCs (see there) */
@@ -525,7 +530,10 @@ int mrx_eligible(int op, size_t nsess, uint32_t pfail);
 #define MPF_MULTI 0x80000000u
 int ms_eligible(int op, size_t nsess, uint32_t pfail);
 int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
-		  struct srtp_batch_dev *d, int counted);
+		  struct srtp_batch_dev *d, int counted, uint32_t *pfail);
+int msrx_eligible(int op, uint32_t pfail);
+int dev_msrxplanned(struct srtp **sessv, size_t nsess,
+		    struct srtp_batch_dev *d);
 int dev_mrxplanned(struct srtp **sessv, size_t nsess,
 		   struct srtp_batch_dev *d);
 

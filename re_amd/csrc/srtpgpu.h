@@ -911,6 +911,42 @@ struct sgpu_bplan_rtps {
 int   sgpu_bplan_rtps_plan(const struct sgpu_bplan_rtps *r, void *stream);
 int   sgpu_bplan_rtps_finish(const struct sgpu_bplan_rtps *r, void *stream);
 
+/*
+ * The receive planner of such an UNPROTECT batch behind a plan of
+ * sgpu_bplan_rtps_plan rejected with SPF_ORDER / SPF_REPLAY only: some stream
+ * of some session arrived reordered, duplicated or replayed
+ * (plan_buckets_rtp_streams_rx.hip; the rule per (session, SSRC):
+ * hip/plan_rtp_seg_rx.h).  toff / recs are the rejected plan's upload, which
+ * nothing modified:
+ *   sgpu_bplan_scatter         again, unchanged (as above)
+ *   sgpu_bplan_rtps_rx_plan    per bucket: the slot and the rank in its stream
+ *                              of every packet as sgpu_bplan_rtps_plan finds
+ *                              them, then per stream the segmented scan and
+ *                              rx_settle of sgpu_bplan_rx_plan with tags
+ *                              verified behind it; desc, rs[], sout / sinfo,
+ *                              cnt[]; an unsettled packet or a failed check:
+ *                              out->fail |=, out->skip[0..3] = 1
+ *   (the general crypto kernels as above)
+ *   sgpu_bplan_rtps_rx_finish  if !out->fail and !*nfail: pos / end / err (0
+ *                              or EALREADY) per packet; always: bcount / obins
+ *                              back to zero, out->nfail, *ro, and outbytes
+ *                              from out to outh
+ * out->fail or out->nfail after it: as above.
+ */
+struct sgpu_bplan_rtps_rx {
+	struct sgpu_bplan_rtps s;       /* s.b.prot 0; posw, hdr used */
+	uint8_t *rs;            /* [packet] verdict (RX_OK / RX_DUP) */
+	uint32_t *cnt;          /* nb x 2: late, duplicates per bucket */
+	struct sgpu_bprx_out *ro;       /* inside [out, out + outbytes) */
+	uint32_t lookback;      /* in-stream arrivals searched for a
+				   duplicate's original (RX_LOOKBACK) */
+	uint32_t hmac;          /* HMAC suite: EALREADY packets are not
+				   decrypted */
+};
+int   sgpu_bplan_rtps_rx_plan(const struct sgpu_bplan_rtps_rx *r, void *stream);
+int   sgpu_bplan_rtps_rx_finish(const struct sgpu_bplan_rtps_rx *r,
+				void *stream);
+
 int   sgpu_plan_rtcp(const struct sgpu_rplan_in *in,
 		     const struct sgpu_hdr *hdr, const uint32_t *eix,
 		     const uint32_t *pos, const uint32_t *end,
