@@ -288,7 +288,11 @@ int srtp_alloc_many(struct srtp **srtpv, size_t n, enum srtp_suite suite,
  * plan was rejected for reordered or replayed packets goes straight to the
  * host engine, not to the device receive planner), "nomrplan" (an SRTCP
  * batch over many sessions on device windows goes through the host engine,
- * not the many-session SRTCP planner), "nomsplan" (an RTP batch over many
+ * not the many-session SRTCP planner; the SRTCP receive planner is off with
+ * it), "nomrrxplan" (such an SRTCP unprotect batch whose plan was rejected
+ * for reordered or replayed packets inside some stream goes straight to the
+ * host engine, not to the SRTCP receive planner), "nomsplan" (an RTP batch
+ * over many
  * sessions on device windows whose sessions hold, or gain in the batch,
  * several SSRCs goes through the host engine, not the many-session
  * multi-SSRC planner), "nomsrxplan" (such an unprotect batch whose plan was
@@ -331,7 +335,12 @@ int srtp_gpu_tune(const char *name, long value);
  * replayed, completed by the multi-SSRC receive planner behind a rejected
  * in-order plan; "rxlate" and "rxdups" count its packets too, "msplans",
  * "mplans" and "mrxplans" do not move for them; srtp_gpu_tune "nomsrxplan"
- * sends them through the host engine).  0 for an unknown name.
+ * sends them through the host engine), "mrrxplans" (SRTCP unprotect batches
+ * over many sessions, HMAC suites, whose streams arrived reordered,
+ * duplicated or replayed, completed by the SRTCP receive planner behind a
+ * rejected in-order plan; "rxlate" and "rxdups" count its packets too,
+ * "mrplans" does not move for them and "rejects" moves once; srtp_gpu_tune
+ * "nomrrxplan" sends them through the host engine).  0 for an unknown name.
  */
 uint64_t srtp_gpu_counter(const char *name);
 

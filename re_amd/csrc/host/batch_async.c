@@ -433,7 +433,12 @@ static int run_dev(int op, struct srtp **sessv, size_t nsess,
 	 * over the host's stream tables (current after sess_host) */
 	if ((op == OP_RTCP_ENC || op == OP_RTCP_DEC) && nsess > 1 && d->sess &&
 	    !g_env.noplan && !g_env.general && !g_env.nomrplan) {
-		int r = dev_mplanned_rtcp(op, sessv, nsess, d);
+		uint32_t pf = 0;
+		int r = dev_mplanned_rtcp(op, sessv, nsess, d, &pf);
+		/* reordered or replayed arrivals inside some stream: the receive
+		 * planner on the tables that plan uploaded */
+		if (r == -1 && mrrx_eligible(op, sessv[0], pf))
+			r = dev_mrrxplanned(sessv, nsess, d);
 		if (r >= 0)
 			return r;
 	}

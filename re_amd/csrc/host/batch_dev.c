@@ -7,7 +7,8 @@
  * dev_planned picks among the three), reordered arrivals (plan_rx.hip),
  * several streams of one session (plan_streams.hip), SRTCP
  * (dev_planned_rtcp; many sessions with up to 8 SSRCs each:
- * plan_buckets_rtcp.hip, dev_mplanned_rtcp), many sessions with resident
+ * plan_buckets_rtcp.hip, dev_mplanned_rtcp, and their reordered or replayed
+ * arrivals: plan_buckets_rtcp_rx.hip, dev_mrrxplanned), many sessions with resident
  * state (dev_mplanned) and their reordered arrivals (plan_buckets_rx.hip,
  * dev_mrxplanned), many sessions with up to 8 SSRCs each
  * (plan_buckets_rtp_streams.hip, dev_msplanned) and their reordered
@@ -1322,7 +1323,8 @@ static size_t al256(size_t x)
  * not resident).  One pass over the sessions gathers the tables
  * (mrplan_gather), one upload, sgpu_bplan_rtcp_scatter / _plan, the compact
  * crypto kernels with per-packet keys guarded by the plan, _finish, one copy
- * back of the touched tables, one synchronisation, the apply.
+ * back of the touched tables, one synchronisation, the apply.  *pfail: a
+ * rejected plan's SPF_* bits (0 otherwise).
  * 0: done; -1: a batch the geometry or the gather does not take (nothing
  * counted), a rejected plan, or a forged packet (undone) -- nothing
  * modified, the caller's fallback continues; errno.
@@ -1332,7 +1334,7 @@ static size_t al256(size_t x)
  * zero between calls) | bucket entries | fail words.
  */
 int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
-		      struct srtp_batch_dev *d)
+		      struct srtp_batch_dev *d, uint32_t *pfail)
 {
 	const int prot = op == OP_RTCP_ENC;
 	const struct comp *c0 = &sessv[0]->rtcp;
@@ -1362,6 +1364,7 @@ int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 	double t[4];
 	int err;
 
+	*pfail = 0;
 	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
 		return -1;
 	w = ws_get();
@@ -1464,6 +1467,7 @@ int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 			fprintf(stderr, "re_srtp mrtcp plan n=%zu nsess=%zu %s: "
 				"rejected (SPF %#x)\n", n, nsess,
 				prot ? "protect" : "unprotect", po->fail);
+		*pfail = po->fail;
 		return -1;
 	}
 	count(&g_cnt_mrplans, 1);
@@ -1486,6 +1490,187 @@ int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 			"%.3f submit %.3f wait %.3f apply %.3f ms\n", n, nsess,
 			prot ? "protect" : "unprotect", t[1] - t[0], t[2] - t[1],
 			t[3] - t[2], now_ms() - t[3]);
+	return 0;
+}
+
+/* ---- SRTCP, many sessions, reordered or replayed arrivals -------------- */
+
+/* a rejected plan of dev_mplanned_rtcp the receive planner
+ * (plan_buckets_rtcp_rx.hip) may settle: only an index that is not new and
+ * increasing inside some stream was in its way (HMAC suites: GCM keeps no
+ * SRTCP replay window and its plan takes any order) */
+int mrrx_eligible(int op, const struct srtp *s, uint32_t pfail)
+{
+	return op == OP_RTCP_DEC && s->rtcp.has_hmac && !g_env.nomrplan &&
+	       !g_env.nomrrxplan && pfail && !(pfail & ~(uint32_t)SPF_REPLAY);
+}
+
+/*
+ * A many-session SRTCP unprotect batch behind such a rejection, on this
+ * thread's workspace as dev_mplanned_rtcp left it: the rejected plan modified
+ * nothing, so its upload (w->ms.d: cm | toff | recs) is still the truth and
+ * nothing is gathered or uploaded again.  The bucket scatter again (the
+ * rejected plan's finish zeroed its counters), sgpu_bplan_rtcp_rx_plan, the
+ * compact crypto kernels with per-packet keys guarded by its verdict (an
+ * EALREADY packet: MAC only), sgpu_bplan_rtcp_rx_finish, one copy back of the
+ * touched tables, one synchronisation, the apply (mrplan_apply).
+ * 0: done; -1: not settled, or a forged packet (undone) -- nothing modified,
+ * the caller's fallback continues; errno.
+ *
+ * w->ms, w->mscr as in dev_mplanned_rtcp; w->bp: BP_HEAD | bucket entries |
+ * fail words | per-bucket counts | verdict bytes; w->pl: plan out |
+ * sgpu_bprx_out.
+ */
+int dev_mrrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
+{
+	const struct comp *c0 = &sessv[0]->rtcp;
+	const size_t n = d->n;
+	const uint32_t grow = 4u + c0->tag_len;
+	const size_t na = (n + SGPU_BP_BLOCK * SGPU_BP_PPT - 1) /
+			  (SGPU_BP_BLOCK * SGPU_BP_PPT);
+	const size_t o_toff = al256(nsess * 4);
+	const size_t o_recs = o_toff + al256((nsess + 1) * 4);
+	const size_t o_sout = al256(nsess * 4);
+	const size_t down = o_sout +
+			    nsess * SRTP_MAX_STREAMS * sizeof(struct sgpu_rtcp_rec);
+	const size_t roff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
+		.vs = n * 5 + 64, .cm = 4, .pl = roff + 64, .es = n * 4};
+	struct ws_layout L;
+	struct sgpu_bplan_rtcp_rx X;
+	struct sgpu_bplan_rtcp *R = &X.r;
+	struct sgpu_compact C;
+	struct sgpu_plan_out *po, *po_d;
+	const struct sgpu_bprx_out *ro;
+	uint32_t bshift, nb, cap;
+	size_t o_afail, o_cnt, o_rs;
+	void *stream = d->stream;
+	struct ws *w;
+	int err;
+
+	if (c0->mode == SGPU_MODE_GCM || !c0->has_hmac)
+		return -1;
+	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
+		return -1;
+	w = ws_get();
+	if (!w)
+		return ENOMEM;
+	/* the upload must be the one dev_mplanned_rtcp made: never a new pool */
+	if (w->ms.cap < o_recs + nsess * SRTP_MAX_STREAMS *
+			 sizeof(struct sgpu_rtcp_rec) || w->mscr.cap < down)
+		return -1;
+	o_afail = BP_HEAD + al256((size_t)nb * cap * 16);
+	o_cnt = o_afail + al256(na * 4);
+	o_rs = o_cnt + al256((size_t)nb * 8);
+	err = ws_layout_reserve(w, n, &z, &L);
+	if (!err)
+		err = pool_reserve(w, &w->bp, o_rs + al256(n));
+	if (err)
+		return err;
+	if (w->bp_d != w->bp.d) {
+		/* a new pool (or a call that did not finish): counters from
+		 * zero */
+		err = sgpu_memset(w->bp.d, 0, BP_HEAD, stream);
+		if (err)
+			return err;
+		w->bp_d = w->bp.d;
+	}
+	po = (struct sgpu_plan_out *)w->pl.h;
+	po_d = (struct sgpu_plan_out *)w->pl.d;
+	ro = (const struct sgpu_bprx_out *)(w->pl.h + roff);
+	memset(&X, 0, sizeof(X));
+	rplan_in(&R->in, sessv[0], (uint32_t)n, 0);
+	R->in.ssrc_any = 0;
+	R->in.ssrc = R->in.rtcp_index = 0;
+	R->in.lix = R->in.bitmap = 0;
+	R->nsess = (uint32_t)nsess;
+	R->bshift = bshift;
+	R->nb = nb;
+	R->cap = cap;
+	R->delta = -(int32_t)grow;
+	R->pos = d->pos;
+	R->end = d->end;
+	R->capv = d->cap;
+	R->sess = d->sess;
+	R->endw = d->end;
+	R->err = d->err;
+	R->es = L.es;
+	R->hdr = L.hdr;
+	R->desc = L.desc;
+	R->bcount = (uint32_t *)(w->bp.d + 512);
+	R->tmp = (void *)(w->bp.d + BP_HEAD);
+	R->afail = (uint32_t *)(w->bp.d + o_afail);
+	R->toff = (const uint32_t *)(w->ms.d + o_toff);
+	R->recs = (const struct sgpu_rtcp_rec *)(w->ms.d + o_recs);
+	R->sinfo = (uint32_t *)w->mscr.d;
+	R->sout = (struct sgpu_rtcp_rec *)(w->mscr.d + o_sout);
+	R->out = po_d;
+	R->nfail = L.nfail;
+	R->outbytes = (uint32_t)(roff + sizeof(struct sgpu_bprx_out));
+	R->outh = g_env.nopost ? NULL : (uint32_t *)po;
+	X.cnt = (uint32_t *)(w->bp.d + o_cnt);
+	X.rs = w->bp.d + o_rs;
+	X.ro = (struct sgpu_bprx_out *)(w->pl.d + roff);
+	X.lookback = RX_LOOKBACK;
+	srv_stop(w);
+	{
+		/* the scatter as the in-order plan launched it (it mirrors
+		 * nothing: the plan out alone is its outbytes) */
+		struct sgpu_bplan_rtcp S = *R;
+		S.outbytes = (uint32_t)offsetof(struct sgpu_plan_out, tail_ix);
+		err = sgpu_bplan_rtcp_scatter(d->arena, d->arena_size, &S, stream);
+	}
+	if (!err)
+		err = sgpu_bplan_rtcp_rx_plan(&X, stream);
+	/* the compact kernels' SRTCP form with per-packet keys (class 2),
+	 * guarded by the plan */
+	C = compact_of(d, &L);
+	C.compmap = (const uint32_t *)w->ms.d;
+	C.sess = d->sess;
+	C.rtcp = 1;
+	C.guard = &po_d->fail;
+	if (!err)
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, 2, 0, stream);
+	if (!err)
+		err = sgpu_bplan_rtcp_rx_finish(&X, stream);
+	if (!err && g_env.nopost)
+		err = sgpu_memcpy_d2h(po, po_d, R->outbytes, stream);
+	if (!err)
+		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, down, stream);
+	if (!err)
+		err = sgpu_stream_sync(stream);
+	if (err) {
+		sgpu_stream_sync(stream);
+		w->bp_d = NULL;
+		return err;
+	}
+	if (po->fail) {
+		/* the crypto launch and the results did nothing (the rejection
+		 * was counted: dev_mplanned_rtcp's) */
+		if (g_env.times)
+			fprintf(stderr, "re_srtp mrrx plan n=%zu nsess=%zu: not "
+				"settled (SPF %#x)\n", n, nsess, po->fail);
+		return -1;
+	}
+	count(&g_cnt_mrrxplans, 1);
+	if (po->nfail) {
+		/* a forged packet: undo on the device (no result was written,
+		 * the host's tables are as they were), fold on the host engine */
+		count(&g_cnt_misses, po->nfail);
+		count(&g_cnt_folds, 1);
+		C.undo = 1;
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, 2, 0, stream);
+		if (!err)
+			err = sgpu_stream_sync(stream);
+		return err ? err : -1;
+	}
+	count(&g_cnt_rxlate, ro->nlate);
+	count(&g_cnt_rxdups, ro->ndup);
+	mrplan_apply(sessv, nsess, 0, (const uint32_t *)w->mscr.h,
+		     (const struct sgpu_rtcp_rec *)(w->mscr.h + o_sout));
 	return 0;
 }
 

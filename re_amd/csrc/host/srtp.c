@@ -129,6 +129,10 @@ uint64_t g_cnt_mplans;   /* multi-session device plans accepted */
 uint64_t g_cnt_rplans;   /* SRTCP device plans (k_plan_rtcp) accepted */
 uint64_t g_cnt_mrplans;  /* many-session SRTCP device plans
 				   (plan_buckets_rtcp.hip) accepted */
+uint64_t g_cnt_mrrxplans; /* ... reordered / replayed unprotect batches
+				   completed by the receive planner
+				   (plan_buckets_rtcp_rx.hip); rxlate and rxdups
+				   count its packets too */
 uint64_t g_cnt_msplans;  /* many-session RTP device plans over sessions of
 				   several SSRCs (plan_buckets_rtp_streams.hip)
 				   accepted */
@@ -219,6 +223,8 @@ uint64_t srtp_gpu_counter(const char *name)
 		return __atomic_load_n(&g_cnt_rplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "mrplans"))
 		return __atomic_load_n(&g_cnt_mrplans, __ATOMIC_RELAXED);
+	if (!strcmp(name, "mrrxplans"))
+		return __atomic_load_n(&g_cnt_mrrxplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "msplans"))
 		return __atomic_load_n(&g_cnt_msplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "msrxplans"))
@@ -320,6 +326,8 @@ int srtp_gpu_tune(const char *name, long value)
 		g_env.norxplan = value > 0;
 	else if (!strcmp(name, "nomrplan"))
 		g_env.nomrplan = value > 0;
+	else if (!strcmp(name, "nomrrxplan"))
+		g_env.nomrrxplan = value > 0;
 	else if (!strcmp(name, "nomsplan"))
 		g_env.nomsplan = value > 0;
 	else if (!strcmp(name, "nomsrxplan"))

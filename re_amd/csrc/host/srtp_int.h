@@ -141,7 +141,12 @@ struct srtp_env {
 				   batches on device windows go through the
 				   host engine (dev_staged), not the bucket
 				   planner (plan_buckets_rtcp.hip) */
-	int smallsync;          /* srtp_gpu_tune smallsync: wait for a small
+	int nomrrxplan;         /* srtp_gpu_tune nomrrxplan: such an unprotect
+				   batch whose plan was rejected for reordered
+				   or replayed packets goes straight to the
+				   host engine, not to the receive planner of
+				   plan_buckets_rtcp_rx.hip */
+	int smallsync;         /* srtp_gpu_tune smallsync: wait for a small
 				   launch by a stream synchronisation, not
 				   its completion word */
 	int lplan;              /* srtp_gpu_tune lplan: single-stream AES-CM
@@ -300,6 +305,7 @@ extern uint64_t g_cnt_splans, g_cnt_fused, g_cnt_gated;
 extern uint64_t g_cnt_dplans, g_cnt_mplans, g_cnt_rplans, g_cnt_lbtimeout;
 extern uint64_t g_cnt_lplans, g_cnt_mrplans, g_cnt_msplans, g_cnt_msrxplans;
 extern uint64_t g_cnt_rxplans, g_cnt_rxlate, g_cnt_rxdups, g_cnt_mrxplans;
+extern uint64_t g_cnt_mrrxplans;
 extern int g_fresh_multi;       /* srtp.c: the last first batch of a session
 				   showed several SSRCs (see there) */
 extern __thread struct tk_owner *t_own; /* srtp.c: this thread's async
@@ -517,7 +523,10 @@ int dev_splanned_finish(struct dcall *k);
 int dev_splanned(int op, struct srtp *s, struct srtp_batch_dev *d);
 int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d);
 int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
-		      struct srtp_batch_dev *d);
+		      struct srtp_batch_dev *d, uint32_t *pfail);
+int mrrx_eligible(int op, const struct srtp *s, uint32_t pfail);
+int dev_mrrxplanned(struct srtp **sessv, size_t nsess,
+		    struct srtp_batch_dev *d);
 int dev_mplanned_issue(struct dcall *k);
 int dev_mplanned_finish(struct dcall *k);
 int dev_mplanned_(int op, struct srtp **sessv, size_t nsess,

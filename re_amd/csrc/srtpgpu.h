@@ -862,6 +862,39 @@ int   sgpu_bplan_rtcp_plan(const struct sgpu_bplan_rtcp *r, void *stream);
 int   sgpu_bplan_rtcp_finish(const struct sgpu_bplan_rtcp *r, void *stream);
 
 /*
+ * The receive planner of such an UNPROTECT batch (HMAC suites) behind a plan
+ * of sgpu_bplan_rtcp_plan rejected with SPF_REPLAY only: some stream of some
+ * session arrived reordered, duplicated or replayed (plan_buckets_rtcp_rx.hip;
+ * the rule per (session, SSRC): hip/plan_rtcp_seg_rx.h).  toff / recs are the
+ * rejected plan's upload, which nothing modified:
+ *   sgpu_bplan_rtcp_scatter    again, unchanged
+ *   sgpu_bplan_rtcp_rx_plan    per bucket: the slot and the rank in its stream
+ *                              of every packet as sgpu_bplan_rtcp_plan finds
+ *                              them, then per stream the segmented scan of
+ *                              the indices and rx_replay with tags verified
+ *                              behind it; desc (an EALREADY packet's with E
+ *                              clear), rs[], sout / sinfo, cnt[]; an unsettled
+ *                              packet or a failed check: out->fail |=
+ *   (the compact crypto kernels as above)
+ *   sgpu_bplan_rtcp_rx_finish  if !out->fail and !*nfail: end / err (0 or
+ *                              EALREADY) per packet; always: bcount back to
+ *                              zero, out->nfail, *ro, and outbytes from out to
+ *                              outh
+ * out->fail or out->nfail after it: as above.
+ */
+struct sgpu_bplan_rtcp_rx {
+	struct sgpu_bplan_rtcp r;       /* r.in: prot 0, gcm 0, hmac 1 */
+	uint8_t *rs;            /* [packet] verdict (RX_OK / RX_DUP) */
+	uint32_t *cnt;          /* nb x 2: late, duplicates per bucket */
+	struct sgpu_bprx_out *ro;       /* inside [out, out + outbytes) */
+	uint32_t lookback;      /* in-stream arrivals searched for a
+				   duplicate's original (RX_LOOKBACK) */
+};
+int   sgpu_bplan_rtcp_rx_plan(const struct sgpu_bplan_rtcp_rx *r, void *stream);
+int   sgpu_bplan_rtcp_rx_finish(const struct sgpu_bplan_rtcp_rx *r,
+				void *stream);
+
+/*
  * RTP batches over many sessions with up to 8 SSRCs each, in order per
  * stream, planned on the device behind the bucket planner
  * (plan_buckets_rtp_streams.hip; the rule per (session, SSRC):

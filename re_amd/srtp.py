@@ -601,7 +601,9 @@ def batch_wait(ticket):
 
 
 def counter(name):
-    """srtp_gpu_counter: "misses", "folds", "rejects" since load"""
+    """srtp_gpu_counter: "misses", "folds", "rejects", the planners'
+    ("mrplans", "mrrxplans", "msplans", "msrxplans", "rxlate", "rxdups", ...)
+    since load; 0 for a name the library does not know"""
     return int(lib().srtp_gpu_counter(name.encode()))
 
 
