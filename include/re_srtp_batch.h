@@ -298,6 +298,10 @@ int srtp_alloc_many(struct srtp **srtpv, size_t n, enum srtp_suite suite,
  * multi-SSRC planner), "nomsrxplan" (such an unprotect batch whose plan was
  * rejected for reordered or replayed packets inside some stream goes
  * straight to the host engine, not to the multi-SSRC receive planner),
+ * "nosrxplan" (an unprotect batch of one session over several SSRCs whose
+ * per-stream device plan was rejected for reordered or replayed packets
+ * inside some stream goes straight to the host engine, not to the
+ * per-stream receive planner),
  * "rxseq" (srtp_rx_index* and srtp_rx_fold walk
  * in one sequential pass, not in parallel parts), "freshmulti" (the
  * planner's first-batch hint: 1 sends a session's first batch to the
@@ -340,7 +344,13 @@ int srtp_gpu_tune(const char *name, long value);
  * duplicated or replayed, completed by the SRTCP receive planner behind a
  * rejected in-order plan; "rxlate" and "rxdups" count its packets too,
  * "mrplans" does not move for them and "rejects" moves once; srtp_gpu_tune
- * "nomrrxplan" sends them through the host engine).  0 for an unknown name.
+ * "nomrrxplan" sends them through the host engine), "srxplans" (unprotect
+ * batches of one session over up to 8 SSRCs whose streams arrived reordered,
+ * with gaps, duplicated or replayed, completed by the per-stream receive
+ * planner behind a rejected per-stream plan; "rxlate" and "rxdups" count its
+ * packets too, "splans" does not move for them and "rejects" moves as
+ * without it; srtp_gpu_tune "nosrxplan" sends them through the host engine).
+ * 0 for an unknown name.
  */
 uint64_t srtp_gpu_counter(const char *name);
 

@@ -31,19 +31,20 @@
  *   k_sp_final  launch guards of the crypto kernels
  *
  * Any verification miss (or a 9th stream) sets out->base.fail: the host
- * then plans sequentially and the guarded launches do nothing.
+ * then plans sequentially and the guarded launches do nothing -- or, where
+ * only the order or a replayed index was in the way of an unprotect batch,
+ * plan_streams_rx.hip plans it exactly, on the same stream table
+ * (sgpu_splan_table: k_sp_ssrc and k_sp_merge alone; plan_streams_tab.h).
  */
 #include <hip/hip_runtime.h>
 #include <errno.h>
 #include <stdio.h>
 #include "../srtpgpu.h"
 #include "plan_common.h"
+#include "plan_streams_tab.h"
 
-#define SP_BLOCK 1024
 #define SP_WAVES (SP_BLOCK / 64)
-#define SP_K SGPU_SP_MAX
 #define SP_SCAN 1024
-#define SP_H 16                 /* per-block SSRC hash slots */
 
 /* the blocks' distinct SSRCs: SP_H hash slots per block, stored slot-major
  * (structure of arrays, nb words per row: consecutive blocks coalesce):
@@ -206,17 +207,6 @@ __device__ __forceinline__ void sp_scan_add(uint2 (*part)[SP_SCAN], uint2 *tot)
 			tot[q] = all;
 	}
 	__syncthreads();
-}
-
-/* slot of SSRC s in the table (SP_K: none) */
-__device__ __forceinline__ uint32_t sp_slot(const uint32_t *tab, uint32_t nt,
-					    uint32_t s)
-{
-	uint32_t k = SP_K;
-	for (uint32_t q = 0; q < nt; q++)
-		if (tab[q] == s)
-			k = q;
-	return k;
 }
 
 __global__ void __launch_bounds__(SP_SCAN)
@@ -589,16 +579,36 @@ __global__ void k_sp_final(struct sgpu_splan_out *out)
 			(((out->base.hl0 >> 2) & 3u) != threadIdx.x);
 }
 
-static size_t sp_al(size_t x)
+/* bl | bprev */
+extern "C" size_t sgpu_splan_table_scratch(uint32_t n)
 {
-	return (x + 255) & ~(size_t)255;
+	const size_t nb = ((size_t)n + SP_BLOCK - 1) / SP_BLOCK;
+	return sp_al(nb * 3 * SP_H * 4) + sp_al(nb * SP_K * 4);
+}
+
+extern "C" int sgpu_splan_table(const struct sgpu_splan_in *in,
+				const struct sgpu_hdr *hdr, void *scratch,
+				struct sgpu_splan_out *out, void *stream)
+{
+	hipStream_t st = (hipStream_t)stream;
+	const uint32_t n = in->n;
+	const uint32_t nb = (n + SP_BLOCK - 1) / SP_BLOCK;
+	uint32_t *bl = (uint32_t *)scratch;
+	int32_t *bprev = (int32_t *)((uint8_t *)scratch +
+				     sp_al((size_t)nb * 3 * SP_H * 4));
+	if (!n || in->nst > SP_K)
+		return EINVAL;
+	hipLaunchKernelGGL(k_sp_ssrc, dim3(nb), dim3(SP_BLOCK), 0, st, hdr, n,
+			   bl, out);
+	hipLaunchKernelGGL(k_sp_merge, dim3(1), dim3(SP_SCAN), 0, st, *in,
+			   (const uint32_t *)bl, nb, bprev, out);
+	return hipGetLastError() == hipSuccess ? 0 : EIO;
 }
 
 extern "C" size_t sgpu_splan_scratch(uint32_t n)
 {
 	const size_t nb = (n + SP_BLOCK - 1) / SP_BLOCK;
-	return sp_al(nb * 3 * SP_H * 4) +              /* bl */
-	       sp_al(nb * SP_K * 4) +                  /* bprev */
+	return sgpu_splan_table_scratch(n) +           /* bl, bprev */
 	       sp_al(nb * SP_K * 4) +                  /* bcnt */
 	       sp_al(nb * SP_K * 8) +                  /* bpre */
 	       sp_al((size_t)n * 4) * 2;               /* rec, prv */
@@ -633,10 +643,8 @@ extern "C" int sgpu_splan_rtp(const struct sgpu_splan_in *in,
 		if (e != hipSuccess)
 			return EIO;
 	}
-	hipLaunchKernelGGL(k_sp_ssrc, dim3(nb), dim3(SP_BLOCK), 0, st, hdr, n,
-			   bl, out);
-	hipLaunchKernelGGL(k_sp_merge, dim3(1), dim3(SP_SCAN), 0, st, *in,
-			   (const uint32_t *)bl, nb, bprev, out);
+	if (sgpu_splan_table(in, hdr, bl, out, stream))
+		return EIO;
 	hipLaunchKernelGGL(k_sp_count, dim3(nb), dim3(SP_BLOCK), 0, st, *in,
 			   hdr, pos, end, cap, arena_size,
 			   (const int32_t *)bprev, rec, prv, bcnt, out);

@@ -90,8 +90,17 @@ static void tk_finish_one(void)
 	if (r == -1) {
 		r = sess_host(k->sessv, k->nsess);
 		/* a second SSRC in a single-stream plan: the per-stream one */
-		if (!r && t->kind == TK_PLANNED && (k->pfail & SPF_SSRC))
-			r = dev_splanned(k->op, k->sessv[0], &k->d);
+		if (!r && t->kind == TK_PLANNED && (k->pfail & SPF_SSRC)) {
+			uint32_t pf = 0;
+			r = dev_splanned(k->op, k->sessv[0], &k->d, &pf);
+			if (r == -1 && srx_eligible(k->op, k->nsess, &k->d, pf))
+				r = dev_srxplanned(k->sessv[0], &k->d);
+		}
+		/* reordered or replayed arrivals inside some stream of a
+		 * per-stream plan: its receive planner */
+		else if (!r && t->kind == TK_SPLANNED &&
+			 srx_eligible(k->op, k->nsess, &k->d, k->pfail))
+			r = dev_srxplanned(k->sessv[0], &k->d);
 		/* a session over the counting grouping's bound: the radix
 		 * sort */
 		else if (!r && t->kind == TK_MPLANNED && (k->pfail & SPF_SEG) &&
@@ -414,8 +423,13 @@ static int run_dev(int op, struct srtp **sessv, size_t nsess,
 		    (sessv[0]->nstreams ||
 		     !__atomic_load_n(&g_fresh_multi, __ATOMIC_RELAXED)))
 			r = dev_planned(op, sessv[0], d, &pf);
-		if (r == -1 && (pf & SPF_SSRC))
-			r = dev_splanned(op, sessv[0], d);
+		if (r == -1 && (pf & SPF_SSRC)) {
+			r = dev_splanned(op, sessv[0], d, &pf);
+			/* reordered or replayed arrivals inside some stream: the
+			 * per-stream receive planner */
+			if (r == -1 && srx_eligible(op, nsess, d, pf))
+				r = dev_srxplanned(sessv[0], d);
+		}
 		/* reordered or replayed arrivals: the receive planner */
 		else if (r == -1 && rx_eligible(op, sessv[0], pf))
 			r = dev_rxplanned(sessv[0], d, NULL, NULL, NULL);

@@ -5,7 +5,8 @@
  * one-launch planner in front of it (k_ctr_fused.h, fz_issue / fz_finish),
  * one stream by the separate planner kernels (dp_issue / dp_finish;
  * dev_planned picks among the three), reordered arrivals (plan_rx.hip),
- * several streams of one session (plan_streams.hip), SRTCP
+ * several streams of one session (plan_streams.hip) and their reordered
+ * arrivals (plan_streams_rx.hip, dev_srxplanned), SRTCP
  * (dev_planned_rtcp; many sessions with up to 8 SSRCs each:
  * plan_buckets_rtcp.hip, dev_mplanned_rtcp, and their reordered or replayed
  * arrivals: plan_buckets_rtcp_rx.hip, dev_mrrxplanned), many sessions with resident
@@ -1047,13 +1048,152 @@ int dev_splanned_finish(struct dcall *k)
 				  prot, d->stream), d, L.es);
 }
 
-/* synchronous: -1 not plannable or folded on the host (nothing
- * modified), else 0 / errno */
-int dev_splanned(int op, struct srtp *s, struct srtp_batch_dev *d)
+/* synchronous: -1 not plannable (*pfail: why) or folded on the host (0)
+ * -- nothing modified --, else 0 / errno */
+int dev_splanned(int op, struct srtp *s, struct srtp_batch_dev *d,
+		 uint32_t *pfail)
 {
-	uint32_t pf;
 	return dev_call(op, &s, 1, d, 0, dev_splanned_issue,
-			dev_splanned_finish, 0, &pf);
+			dev_splanned_finish, 0, pfail);
+}
+
+/* ---- one session, several streams, reordered / duplicated arrivals ---- */
+/* (plan_streams_rx.hip) */
+
+/* a rejected per-stream unprotect plan the receive planner may settle: only
+ * the arrival order or a replayed index inside some stream was in its way */
+int srx_eligible(int op, size_t nsess, const struct srtp_batch_dev *d,
+		 uint32_t pfail)
+{
+	return op == OP_RTP_DEC && nsess == 1 && !d->sess && !g_env.nosrxplan &&
+	       pfail && !(pfail & ~(uint32_t)(SPF_ORDER | SPF_REPLAY));
+}
+
+/*
+ * One-session unprotect batch over several SSRCs behind such a rejection:
+ * the parse prologue, sgpu_splan_rx, the general descriptor-driven crypto
+ * launches guarded by its verdict, the guarded results, one copy back, one
+ * synchronisation; then the streams the batch opened are appended in
+ * first-appearance order and every touched stream takes its record after the
+ * batch.  0: done; -1: not settled, or a forged packet (undone) -- nothing
+ * modified, the caller's fallback continues; errno.
+ */
+int dev_srxplanned(struct srtp *s, struct srtp_batch_dev *d)
+{
+	const struct comp *c0 = &s->rtp;
+	const int gcm = c0->mode == SGPU_MODE_GCM;
+	const size_t n = d->n;
+	const uint32_t T = gcm ? 16u : c0->tag_len;
+	const size_t scr = sgpu_splan_rx_scratch((uint32_t)n);
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
+		.vs = n * 5 + 64, .cm = 4,
+		.pl = 64 + sizeof(struct sgpu_srxplan_out), .es = n * 4};
+	struct ws_layout L;
+	struct sgpu_compact C;
+	struct sgpu_srxplan_in in;
+	struct sgpu_srxplan_out *ro, *ro_d;
+	void *stream = d->stream;
+	struct ws *w = ws_get();
+	unsigned k;
+	int err, q;
+
+	if (!w)
+		return ENOMEM;
+	/* the rule computes in signed 64 bits (an imported window) */
+	for (k = 0; k < s->nstreams; k++)
+		if (s->streams[k].replay_rtp.lix >> 62)
+			return -1;
+	err = ws_layout_reserve(w, n, &z, &L);
+	if (!err)
+		err = pool_reserve(w, &w->mscr, scr);
+	if (err)
+		return err;
+	ro = (struct sgpu_srxplan_out *)w->pl.h;
+	ro_d = (struct sgpu_srxplan_out *)w->pl.d;
+
+	memset(&in, 0, sizeof(in));
+	splan_in(&in.s, s, (uint32_t)n, 0, T, 0);
+	in.s.zeroed = 1;
+	in.hmac = !gcm;
+	in.lookback = RX_LOOKBACK;
+	{
+		/* one launch: parse + end copy + zeroed plan out + comp map */
+		struct sgpu_prologue pro = {
+			.end_copy = L.es, .z0 = (uint32_t *)ro_d,
+			.nz0 = (uint32_t)(sizeof(*ro) / 4), .cm_out = L.cm,
+			.cm = c0->dev};
+		err = sgpu_parse_prologue(d->arena, d->arena_size, d->pos,
+					  d->end, L.hdr, NULL, (uint32_t)n, 0,
+					  &pro, stream);
+	}
+	if (!err)
+		err = sgpu_splan_rx(&in, L.hdr, d->pos, L.es, d->cap,
+				    d->arena_size, L.desc, w->mscr.d, scr, ro_d,
+				    stream);
+	/* the general kernels (EALREADY packets: MAC only): AES-CM picks the
+	 * header class from skip[], GCM has one */
+	C = compact_of(d, &L);
+	C.nfail = &ro_d->tab.base.nfail;
+	C.uniform = 1;
+	C.guard = gcm ? &ro_d->tab.base.fail : ro_d->tab.base.skip;
+	if (!err)
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, gcm ? 0 : -1, 0, stream);
+	if (!err)
+		err = sgpu_splan_rx_commit(ro_d, L.hdr, w->mscr.d, L.es, d->pos,
+					   d->end, d->err, (uint32_t)n, T, stream);
+	if (!err)
+		err = sgpu_memcpy_d2h(ro, ro_d, sizeof(*ro), stream);
+	if (!err)
+		err = sgpu_stream_sync(stream);
+	if (err)
+		return err;
+	if (ro->tab.base.fail) {
+		if (g_env.times)
+			fprintf(stderr, "re_srtp streams rx plan n=%zu: not settled "
+				"(SPF %#x)\n", n, ro->tab.base.fail);
+		return -1;
+	}
+	if (ro->tab.base.nfail) {
+		/* a forged packet: undo on the device (the results were not
+		 * written), fold on the host engine -- which counts the misses
+		 * and the one fold, as it does without this planner */
+		/* AES-CM: one guarded launch per header class, GCM: one */
+		C.undo = 1;
+		for (q = 0; q < (gcm ? 1 : 4) && !err; q++) {
+			C.guard = gcm ? &ro_d->tab.base.fail
+				      : &ro_d->tab.base.skip[q];
+			err = sgpu_run_compact(d->arena, d->arena_size, &C,
+					       c0->mode, (int)c0->nr, q, 0, stream);
+		}
+		if (!err)
+			err = sgpu_stream_sync(stream);
+		return err ? err : -1;
+	}
+	/* new SSRCs in first-appearance order (stream_new, stream.c:45-67),
+	 * then every touched stream's record after the batch */
+	for (k = 0; k < ro->tab.nst && k < SRTP_MAX_STREAMS; k++) {
+		struct srtp_stream *x = &s->streams[k];
+		const struct sgpu_rtp_rec *a = &ro->after[k];
+		if (k >= s->nstreams) {
+			memset(x, 0, sizeof(*x));
+			x->ssrc = ro->tab.ssrc[k];
+		}
+		if (!ro->cnt[k])
+			continue;
+		x->roc = a->roc;
+		x->s_l = (uint16_t)a->sl;
+		x->s_l_set = 1;
+		x->replay_rtp.lix = (uint64_t)a->lhi << 32 | a->llo;
+		x->replay_rtp.bitmap = (uint64_t)a->bhi << 32 | a->blo;
+	}
+	if (ro->tab.nst > s->nstreams)
+		s->nstreams = ro->tab.nst;
+	count(&g_cnt_srxplans, 1);
+	count(&g_cnt_rxlate, ro->nlate);
+	count(&g_cnt_rxdups, ro->ndup);
+	return 0;
 }
 
 /* the SRTCP plan input of a batch of n packets on session s */

@@ -142,6 +142,11 @@ uint64_t g_cnt_msrxplans; /* ... reordered / duplicated unprotect batches
 				   rxlate and rxdups count its packets too */
 uint64_t g_cnt_lplans;   /* single-stream batches planned by the
 				   one-launch planner (k_lp_plan), accepted */
+uint64_t g_cnt_srxplans; /* reordered / duplicated one-session unprotect
+				   batches over several SSRCs completed by the
+				   per-stream receive planner
+				   (plan_streams_rx.hip); rxlate and rxdups count
+				   its packets too */
 uint64_t g_cnt_rxplans;  /* reordered / duplicated one-stream unprotect
 				   batches completed by the receive planner
 				   (plan_rx.hip) */
@@ -229,6 +234,8 @@ uint64_t srtp_gpu_counter(const char *name)
 		return __atomic_load_n(&g_cnt_msplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "msrxplans"))
 		return __atomic_load_n(&g_cnt_msrxplans, __ATOMIC_RELAXED);
+	if (!strcmp(name, "srxplans"))
+		return __atomic_load_n(&g_cnt_srxplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "lbtimeouts"))
 		return __atomic_load_n(&g_cnt_lbtimeout, __ATOMIC_RELAXED);
 	if (!strcmp(name, "pcbatches"))
@@ -332,6 +339,8 @@ int srtp_gpu_tune(const char *name, long value)
 		g_env.nomsplan = value > 0;
 	else if (!strcmp(name, "nomsrxplan"))
 		g_env.nomsrxplan = value > 0;
+	else if (!strcmp(name, "nosrxplan"))
+		g_env.nosrxplan = value > 0;
 	else if (!strcmp(name, "rxseq"))
 		g_env.rxseq = value > 0;
 	else if (!strcmp(name, "freshmulti"))

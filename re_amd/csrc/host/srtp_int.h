@@ -137,6 +137,12 @@ struct srtp_env {
 				   or replayed packets goes straight to the
 				   host engine, not to the receive planner of
 				   plan_buckets_rtp_streams_rx.hip */
+	int nosrxplan;          /* srtp_gpu_tune nosrxplan: a one-session
+				   unprotect batch over several SSRCs whose
+				   plan was rejected for reordered or replayed
+				   packets goes straight to the host engine,
+				   not to the receive planner of
+				   plan_streams_rx.hip */
 	int nomrplan;           /* srtp_gpu_tune nomrplan: many-session SRTCP
 				   batches on device windows go through the
 				   host engine (dev_staged), not the bucket
@@ -305,7 +311,7 @@ extern uint64_t g_cnt_splans, g_cnt_fused, g_cnt_gated;
 extern uint64_t g_cnt_dplans, g_cnt_mplans, g_cnt_rplans, g_cnt_lbtimeout;
 extern uint64_t g_cnt_lplans, g_cnt_mrplans, g_cnt_msplans, g_cnt_msrxplans;
 extern uint64_t g_cnt_rxplans, g_cnt_rxlate, g_cnt_rxdups, g_cnt_mrxplans;
-extern uint64_t g_cnt_mrrxplans;
+extern uint64_t g_cnt_mrrxplans, g_cnt_srxplans;
 extern int g_fresh_multi;       /* srtp.c: the last first batch of a session
 				   showed several SSRCs (see there) */
 extern __thread struct tk_owner *t_own; /* srtp.c: this thread's async
@@ -520,7 +526,11 @@ int dev_rxplanned(struct srtp *s, struct srtp_batch_dev *d, uint32_t *hpos,
 		  uint32_t *hend, int32_t *herr);
 int dev_splanned_issue(struct dcall *k);
 int dev_splanned_finish(struct dcall *k);
-int dev_splanned(int op, struct srtp *s, struct srtp_batch_dev *d);
+int dev_splanned(int op, struct srtp *s, struct srtp_batch_dev *d,
+		 uint32_t *pfail);
+int srx_eligible(int op, size_t nsess, const struct srtp_batch_dev *d,
+		 uint32_t pfail);
+int dev_srxplanned(struct srtp *s, struct srtp_batch_dev *d);
 int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d);
 int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 		      struct srtp_batch_dev *d, uint32_t *pfail);

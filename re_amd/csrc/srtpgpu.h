@@ -514,6 +514,14 @@ int   sgpu_splan_rtp(const struct sgpu_splan_in *in,
 		     uint64_t arena_size, uint64_t *desc, void *scratch,
 		     size_t scratch_bytes, struct sgpu_splan_out *out,
 		     void *stream);
+/* its first two launches alone (k_sp_ssrc, k_sp_merge): the session's stream
+ * table after the batch into out->ssrc[0..out->nst) -- known streams, then new
+ * SSRCs by first appearance -- with SPF_PARSE / SPF_SSRC (a 9th) in
+ * out->base.fail; scratch: sgpu_splan_table_scratch(n) bytes */
+size_t sgpu_splan_table_scratch(uint32_t n);
+int   sgpu_splan_table(const struct sgpu_splan_in *in,
+		       const struct sgpu_hdr *hdr, void *scratch,
+		       struct sgpu_splan_out *out, void *stream);
 
 
 struct sgpu_mplan_in {
@@ -979,6 +987,58 @@ struct sgpu_bplan_rtps_rx {
 int   sgpu_bplan_rtps_rx_plan(const struct sgpu_bplan_rtps_rx *r, void *stream);
 int   sgpu_bplan_rtps_rx_finish(const struct sgpu_bplan_rtps_rx *r,
 				void *stream);
+
+/*
+ * Exact device plan of a single-session RTP UNPROTECT batch over up to
+ * SGPU_SP_MAX streams, any of which arrives reordered, duplicated, with gaps
+ * or replayed (plan_streams_rx.hip; the rule per stream: hip/plan_rx_rule.h
+ * composed by hip/plan_rtp_seg_rx.h) -- what sgpu_splan_rtp rejects with
+ * SPF_ORDER / SPF_REPLAY.  in->s as for sgpu_splan_rtp (prot 0); hdr / pos /
+ * end / cap likewise.  The stream table is sgpu_splan_table's; the packets are
+ * partitioned stably by stream slot, so a stream's arrivals in batch order
+ * are one segment of one segmented (sum, max) scan; rx_settle verifies every
+ * packet with positions local to its segment.  desc as sgpu_plan_rx writes
+ * it.  out->tab.base.fail != 0: not settled, nothing modified, plan on the
+ * host.  out->tab.base.skip[] / fail guard the crypto launches behind it,
+ * which count their tag misses in out->tab.base.nfail; sgpu_splan_rx_commit
+ * behind those writes the caller's pos / end / err (0 or EALREADY) unless
+ * fail or nfail.  Every launch is bounded by its own grid: no workgroup
+ * waits for another.
+ */
+struct sgpu_srxplan_in {
+	struct sgpu_splan_in s;         /* n, tag, maxlen, zeroed, nst, st[] */
+	uint32_t hmac;          /* HMAC suite: EALREADY packets are not
+				   decrypted */
+	uint32_t lookback;      /* in-stream arrivals searched for a
+				   duplicate's original (RX_LOOKBACK) */
+};
+
+struct sgpu_srxplan_out {
+	struct sgpu_splan_out tab;      /* base.fail / nfail / hl0 / skip[], nst,
+					   ssrc[]: the table after the batch */
+	uint32_t nlate;         /* packets accepted below their window's top */
+	uint32_t ndup;          /* EALREADY verdicts */
+	uint32_t cnt[SGPU_SP_MAX];      /* arrivals per slot */
+	uint32_t start[SGPU_SP_MAX];    /* the slot's segment in stream-major
+					   order */
+	uint64_t bits[SGPU_SP_MAX];     /* accepted packets' window bits */
+	struct sgpu_rtp_rec after[SGPU_SP_MAX]; /* touched slots (cnt != 0): the
+						   record after the batch */
+};
+
+unsigned sgpu_splan_rx_block(void);     /* packets per workgroup */
+size_t sgpu_splan_rx_scratch(uint32_t n);
+int   sgpu_splan_rx(const struct sgpu_srxplan_in *in,
+		    const struct sgpu_hdr *hdr, const uint32_t *pos,
+		    const uint32_t *end, const uint32_t *cap,
+		    uint64_t arena_size, uint64_t *desc, void *scratch,
+		    size_t scratch_bytes, struct sgpu_srxplan_out *out,
+		    void *stream);
+/* es: the ends before the call; pos / end / err: the caller's arrays */
+int   sgpu_splan_rx_commit(const struct sgpu_srxplan_out *out,
+			   const struct sgpu_hdr *hdr, const void *scratch,
+			   const uint32_t *es, uint32_t *pos, uint32_t *end,
+			   int32_t *err, uint32_t n, uint32_t tag, void *stream);
 
 int   sgpu_plan_rtcp(const struct sgpu_rplan_in *in,
 		     const struct sgpu_hdr *hdr, const uint32_t *eix,
