@@ -233,8 +233,10 @@ int srtp_rx_fold(struct srtp_stream_state *st, enum srtp_suite suite,
  * batch is settled -- ix[i] is packet i's 48-bit index, err[i] its result
  * (0 or EALREADY) and *st1 the stream after it, all exactly the sequential
  * receiver's.  *fail != 0: the rule cannot settle it (for instance a
- * packet from before a rollover arriving after it: ETIMEDOUT); *st1 = *st0,
- * ix and err are unspecified.  block >= 1.  0, EINVAL or ENOMEM.
+ * packet from before a rollover arriving after it: ETIMEDOUT; or a stream
+ * at, or a batch that reaches, ROC 2^31, where the reference's index is
+ * sign-extended, misc.c:40); *st1 = *st0, ix and err are unspecified.
+ * block >= 1.  0, EINVAL or ENOMEM.
  */
 int srtp_rx_plan_host(const struct srtp_stream_state *st0, const uint16_t *seq,
 		      size_t n, uint32_t block, uint32_t lookback,

@@ -155,6 +155,15 @@ RX_FN int32_t rx_v(uint32_t roc, uint32_t s_l, uint32_t seq)
  * always answers the stream's own ROC -- its roc - 1 branch needs
  * seq - s_l > 32768, its roc + 1 branch seq - s_l < -32768 -- so a
  * different answer is treated as ETIMEDOUT is: not settled here.)
+ *
+ * srtp_get_index holds that ROC in an int and widens it to the 64-bit index
+ * (misc.c:24, 40): from ROC 2^31 on the index the replay window stores is
+ * sign-extended, 0xffff8000_0000_0000 and above.  A step that leaves the ROC
+ * there -- a stream taken over at such a ROC, the rollover that crosses
+ * 2^31, the one behind 2^32 - 1 (the uint32_t ROC is 0 again, the window's
+ * top stays near 2^64) -- is not settled either: H, u[] and the window live
+ * in the signed 48-bit domain below it, and the batch is planned
+ * sequentially with the reference's own arithmetic.
  */
 RX_FN int rx_step(int64_t M, uint32_t seq, int64_t *u, int *bump)
 {
@@ -168,6 +177,8 @@ RX_FN int rx_step(int64_t M, uint32_t seq, int64_t *u, int *bump)
 		roc++;
 		s_l = 0;
 	}
+	if (roc >> 31 || (*bump && !roc))
+		return -1;
 	if ((uint32_t)rx_v(roc, s_l, seq) != roc)
 		return -1;
 	*u = (int64_t)(((uint64_t)roc << 16) | (seq & 0xffffu));
@@ -217,7 +228,11 @@ RX_FN int rx_replay(const int64_t *u, const int64_t *mx, uint32_t i,
  * Packet i settled: RX_OK / RX_DUP are the reference's 0 / EALREADY and
  * u[i] the index it authenticates at.  An EALREADY packet must leave the
  * state as the speculation assumes: one that rolled the ROC over (the
- * reference keeps roc + 1, s_l = 0) or lies above M is unsettled.
+ * reference keeps roc + 1, s_l = 0) or lies above M is unsettled.  So is
+ * every packet of a stream whose window before the batch holds a
+ * sign-extended index (lix0 of 2^62 or more as an unsigned number: the
+ * reference's own from ROC 2^31 on, and still there behind 2^32 when the
+ * ROC is small again): the maxima here are signed.
  */
 RX_FN int rx_settle(const int64_t *u, const int64_t *mx, uint32_t i,
 		    uint32_t seq, uint32_t K, int64_t H0, int64_t lix0,
@@ -226,7 +241,7 @@ RX_FN int rx_settle(const int64_t *u, const int64_t *mx, uint32_t i,
 	const int64_t M = rx_max(H0, mx[i]);
 	int64_t v = 0;
 	int bump = 0, r;
-	if (rx_step(M, seq, &v, &bump) || v != u[i])
+	if ((uint64_t)lix0 >> 62 || rx_step(M, seq, &v, &bump) || v != u[i])
 		return RX_UNSETTLED;
 	r = rx_replay(u, mx, i, K, lix0, bitmap0, tagged);
 	if (r == RX_DUP && (bump || u[i] > M))

@@ -668,10 +668,17 @@ int srtp_rx_plan_host(const struct srtp_stream_state *st0, const uint16_t *seq,
 	int bump = 0;
 
 	if (!st0 || !seq || !n || !block || !ix || !err || !st1 || !fail ||
-	    n > UINT32_MAX || (st0->replay_rtp_lix >> 62))
+	    n > UINT32_MAX)
 		return EINVAL;
 	*st1 = *st0;
 	*fail = 0;
+	/* the rule computes in signed 64 bits: a window at a sign-extended
+	 * index (ROC 2^31 and above, misc.c:40) is not settled, as in
+	 * dev_rxplanned */
+	if (st0->replay_rtp_lix >> 62) {
+		*fail = SPF_REPLAY;
+		return 0;
+	}
 	agg = fi_malloc(nb * sizeof(*agg));
 	u = fi_malloc(n * sizeof(*u));
 	mx = fi_malloc(n * sizeof(*mx));

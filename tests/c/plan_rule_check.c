@@ -203,10 +203,12 @@ static uint32_t fails_of(const struct rx *st, int fresh, const uint16_t *seq,
 
 static void check_index(void)
 {
-	static const uint32_t rocs[] = {0, 1, 0x7fffffffu, 0xffffffffu};
+	static const uint32_t rocs[] = {0, 1, 0xffffu, 0x10000u, 0x7ffffffeu,
+					0x7fffffffu, 0x80000000u, 0xfffffffeu,
+					0xffffffffu};
 	static const uint16_t edge[] = {0, 1, 32767, 32768, 32769, 65535};
 	uint32_t r, k;
-	for (r = 0; r < 4; r++) {
+	for (r = 0; r < sizeof(rocs) / sizeof(rocs[0]); r++) {
 		for (k = 0; k < 36 + 4096; k++) {
 			const uint16_t s_l = k < 36 ? edge[k / 6] : (uint16_t)rnd();
 			const uint16_t seq = k < 36 ? edge[k % 6] : (uint16_t)rnd();
@@ -274,6 +276,21 @@ static void check_accept(void)
 			 * but what is must still be the receiver's) */
 			const struct rx top = continuing(0xfffffffeu, base);
 			(void)check_batch(&top, 0, seq, n, 0, "roc near 2^32");
+			/* its siblings: nothing in the reference is special at
+			 * 2^16; the batches of two rollovers cross 2^31 */
+			const struct rx p16 = continuing(0xfffeu, base);
+			(void)check_batch(&p16, 0, seq, n, 1, "roc near 2^16");
+			const struct rx p31 = continuing(0x7ffffffeu, base);
+			(void)check_batch(&p31, 0, seq, n, 0, "roc near 2^31");
+			/* ... and with the window the reference itself leaves
+			 * at such a ROC: its top sign-extended (misc.c:40) */
+			struct rx sx = continuing(0x80000000u, base);
+			sx.lix = ref_get_index(sx.roc, base, base);
+			(void)check_batch(&sx, 0, seq, n, 0, "roc 2^31, its window");
+			sx = continuing(0xfffffffeu, base);
+			sx.lix = ref_get_index(sx.roc, base, base);
+			(void)check_batch(&sx, 0, seq, n, 0, "roc near 2^32, its "
+					  "window");
 			/* packet 0 inside the stored window, on a clear bit: at or
 			 * above s_l (a step back is SPF_ORDER unless it is the
 			 * batch's last packet), the window's top 20 above it;

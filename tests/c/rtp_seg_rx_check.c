@@ -31,6 +31,12 @@
  * each stream's arrivals, with u[] and mx[] from the serial recurrence,
  * settles every packet (a first step that is an ETIMEDOUT settles nothing).
  *
+ * The worlds run once with the known streams at ROC 0..2 and then with about
+ * a third of them at B - 2 .. B for B = 2^16, 2^31 and 2^32 between the
+ * others.  The sequential receiver widens `int v` as misc.c:40 does, so the
+ * window's top is sign-extended from ROC 2^31 on; a batch in which a stream
+ * crosses 2^31 or 2^32 must be declined, every accepted one is exact.
+ *
  *   rtp_seg_rx_check            the random worlds
  *   rtp_seg_rx_check FILE       a recorded traffic (lines "B", then "session
  *                               ssrc seq" per arrival; tables start empty):
@@ -155,7 +161,7 @@ static void sequential(const struct batch *B, struct tab *t, int *err,
 	for (i = 0; i < B->n; i++) {
 		const struct pkt *p = &B->p[i];
 		struct tseg_rec *st;
-		uint64_t lix, bm;
+		uint64_t lix, bm, ixf;
 		uint32_t s_l, v;
 		int diff;
 		ix[i] = 0;
@@ -176,10 +182,12 @@ static void sequential(const struct batch *B, struct tab *t, int *err,
 		lix = tseg_lix(*st);
 		bm = tseg_bitmap(*st);
 		v = ref_v(st->roc, s_l, p->seq);
-		ix[i] = (p->seq + (uint64_t)(int64_t)(int32_t)v * 65536ull) &
-			0xffffffffffffull;
+		/* misc.c:40: `int v` widened -- the window holds the
+		 * sign-extended index, the IV its low 48 bits */
+		ixf = p->seq + (uint64_t)(int64_t)(int32_t)v * 65536ull;
+		ix[i] = ixf & 0xffffffffffffull;
 		fl[i] = SD_RUN | SD_CIPHER;
-		if (!ref_replay_check(&lix, &bm, ix[i])) {
+		if (!ref_replay_check(&lix, &bm, ixf)) {
 			/* (the rollover above stays, s_l does not; the tag was
 			 * checked before: HMAC suites do not decrypt it) */
 			st->sl = s_l | TSEG_SL_SET;
@@ -539,6 +547,10 @@ static uint32_t ssrc_of(uint32_t s, uint32_t k)
 enum { TR_NINTH = 1, TR_DUP = 2, TR_SWAP = 4, TR_JUMP = 8, TR_REPLAY = 16,
        TR_UNSET = 32, TR_GAP = 64, TR_FAR = 128 };
 
+/* not 0: about a third of the known streams are at ROC g_roc0 + 0..2, the
+ * others beside them at 0..2 as ever */
+static uint32_t g_roc0;
+
 static uint32_t make_world(struct world *W, uint32_t trouble_pm)
 {
 	uint32_t done = 0, s, k;
@@ -564,8 +576,13 @@ static uint32_t make_world(struct world *W, uint32_t trouble_pm)
 				continue;
 			}
 			r->roc = rnd() % 3;
+			if (g_roc0 && chance(300))
+				r->roc += g_roc0;
 			W->nxt[s][k] += 65536ull * r->roc;
-			lix = W->nxt[s][k] - 1;
+			/* the window's top as the reference leaves it
+			 * (misc.c:40) */
+			lix = ((W->nxt[s][k] - 1) & 0xffffu) +
+			      (uint64_t)(int64_t)(int32_t)r->roc * 65536ull;
 			r->sl = (uint32_t)(lix & 0xffffu) | TSEG_SL_SET;
 			r->llo = (uint32_t)lix;
 			r->lhi = (uint32_t)(lix >> 32);
@@ -718,29 +735,29 @@ static int replay_file(const char *path)
 	return 0;
 }
 
-int main(int argc, char **argv)
+/* what a run of random worlds met */
+struct tally {
+	uint32_t naccept, nreject, nmust, seen, nroll, ndups, nlates, nlong;
+	uint32_t nacc_trouble, nnew, ncross;
+};
+
+static void random_worlds(struct world *W, uint32_t nit, struct tally *Y)
 {
-	static struct world W;
 	static struct batch B;
 	static struct tab ts[SMAX], tp[SMAX];
 	static int err[NMAX], vdp[NMAX];
 	static uint64_t ixs[NMAX], ixp[NMAX];
 	static uint32_t fls[NMAX], flp[NMAX];
-	const uint32_t all = TR_NINTH | TR_DUP | TR_SWAP | TR_JUMP | TR_REPLAY |
-			     TR_UNSET | TR_GAP | TR_FAR;
-	uint32_t it, naccept = 0, nreject = 0, nmust = 0, seen = 0, nroll = 0;
-	uint32_t ndups = 0, nlates = 0, nlong = 0, nacc_trouble = 0, nnew = 0;
-
-	if (argc > 1)
-		return replay_file(argv[1]);
-	for (it = 0; it < 6000; it++) {
+	uint32_t it;
+	memset(Y, 0, sizeof(*Y));
+	for (it = 0; it < nit; it++) {
 		struct geo G;
 		const uint32_t pm = it % 8 < 2 ? 0 : it % 8 < 6 ? 60 : 300;
-		uint32_t tr, fail, i, s, k, nl = 0, nd = 0, nea = 0;
+		uint32_t tr, fail, i, s, k, nl = 0, nd = 0, nea = 0, cross = 0;
 		int must;
 
 		if (it % 4 == 0)
-			seen |= make_world(&W, pm);
+			Y->seen |= make_world(W, pm);
 		G.bshift = rnd() % 4;
 		G.segmax = chance(850) ? NMAX : 8 + rnd() % 64;
 		G.W = 1u << (1 + rnd() % 4);            /* 2 .. 16 */
@@ -748,27 +765,38 @@ int main(int argc, char **argv)
 		G.ept = 1 + rnd() % 4;
 		if (chance(850))                        /* cap >= the batch */
 			G.ept = (NMAX + G.T - 1) / G.T;
-		tr = make_batch(&W, &B, pm);
+		tr = make_batch(W, &B, pm);
 		sequential(&B, ts, err, ixs, fls);
 		memset(ixp, 0, sizeof(ixp));
 		memset(flp, 0, sizeof(flp));
 		memset(vdp, 0, sizeof(vdp));
 		fail = planned(&B, G, tp, ixp, flp, vdp, &nl, &nd);
 		must = must_accept(&B, G, err);
-		nmust += (uint32_t)must;
-		seen |= tr;
+		Y->nmust += (uint32_t)must;
+		Y->seen |= tr;
 		CHECK(!(must && fail), "it %u: rejected (SPF %#x) a batch it must "
 		      "accept", it, fail);
 		CHECK(must || fail, "it %u: accepted a batch the sequential "
 		      "rx_settle does not settle", it);
+		/* a stream the receiver took across ROC 2^31 or 2^32: its index
+		 * is sign-extended from there on, the planner must decline */
+		for (s = 0; s < B.nsess; s++)
+			for (k = 0; k < B.t0[s].n; k++) {
+				const uint32_t r0 = B.t0[s].st[k].roc;
+				const uint32_t r1 = ts[s].st[k].roc;
+				cross |= (!(r0 >> 31) && (r1 >> 31)) || r1 < r0;
+			}
+		Y->ncross += cross;
+		CHECK(!cross || fail, "roc %#x it %u: accepted a batch that crosses "
+		      "2^31 or 2^32", g_roc0, it);
 		/* the next batch starts from what the receiver holds */
-		memcpy(W.t, ts, sizeof(W.t));
+		memcpy(W->t, ts, sizeof(W->t));
 		if (fail) {
-			nreject++;
+			Y->nreject++;
 			continue;
 		}
-		naccept++;
-		nacc_trouble += (tr & (TR_DUP | TR_SWAP | TR_REPLAY)) != 0;
+		Y->naccept++;
+		Y->nacc_trouble += (tr & (TR_DUP | TR_SWAP | TR_REPLAY)) != 0;
 		for (i = 0; i < B.n; i++) {
 			CHECK(err[i] == 0 || err[i] == EALREADY, "it %u: accepted, "
 			      "packet %u has errno %d", it, i, err[i]);
@@ -783,13 +811,13 @@ int main(int argc, char **argv)
 		}
 		CHECK(nd == nea, "it %u: %u duplicates counted, sequential %u", it,
 		      nd, nea);
-		ndups += nd;
-		nlates += nl;
+		Y->ndups += nd;
+		Y->nlates += nl;
 		for (s = 0; s < B.nsess; s++) {
 			uint32_t per[KMAX] = {0};
 			CHECK(tp[s].n == ts[s].n, "it %u: session %u has %u "
 			      "streams, sequential %u", it, s, tp[s].n, ts[s].n);
-			nnew += ts[s].n - B.t0[s].n;
+			Y->nnew += ts[s].n - B.t0[s].n;
 			for (k = 0; k < ts[s].n && k < tp[s].n; k++) {
 				const struct tseg_rec *a = &tp[s].st[k];
 				const struct tseg_rec *c = &ts[s].st[k];
@@ -801,26 +829,62 @@ int main(int argc, char **argv)
 				      a->bhi, a->blo, c->ssrc, c->roc, c->sl,
 				      c->lhi, c->llo, c->bhi, c->blo);
 				if (k < B.t0[s].n && c->roc != B.t0[s].st[k].roc)
-					nroll++;
+					Y->nroll++;
 			}
 			for (i = 0; i < B.n; i++)
 				if (B.p[i].sess == s)
 					per[B.p[i].ssrc & 0xffu]++;
 			for (k = 0; k < KMAX; k++)
-				nlong += per[k] > 4 * G.W;
+				Y->nlong += per[k] > 4 * G.W;
 		}
 	}
+}
+
+int main(int argc, char **argv)
+{
+	static struct world W;
+	static const uint32_t BASE[3] = {0xfffeu, 0x7ffffffeu, 0xfffffffeu};
+	const uint32_t all = TR_NINTH | TR_DUP | TR_SWAP | TR_JUMP | TR_REPLAY |
+			     TR_UNSET | TR_GAP | TR_FAR;
+	struct tally Y, Z;
+	uint32_t b;
+
+	if (argc > 1)
+		return replay_file(argv[1]);
+	random_worlds(&W, 6000, &Y);
 	/* the run met what it is about */
-	CHECK(naccept > 1500 && nreject > 300, "accepted %u rejected %u", naccept,
-	      nreject);
-	CHECK(nacc_trouble > 300, "accepted batches with swaps, duplicates or "
-	      "replays %u", nacc_trouble);
-	CHECK(ndups > 300 && nlates > 300, "duplicates %u late %u", ndups, nlates);
-	CHECK(nroll > 300, "rollovers inside accepted batches %u", nroll);
-	CHECK(nnew > 300, "streams opened in accepted batches %u", nnew);
-	CHECK(nlong > 300, "streams across several waves %u", nlong);
-	CHECK((seen & all) == all, "seen %#x", seen);
-	printf("%u batches: %u accepted (%u must), %u rejected, %d wrong\n", it,
-	       naccept, nmust, nreject, g_bad);
+	CHECK(Y.naccept > 1500 && Y.nreject > 300, "accepted %u rejected %u",
+	      Y.naccept, Y.nreject);
+	CHECK(Y.nacc_trouble > 300, "accepted batches with swaps, duplicates or "
+	      "replays %u", Y.nacc_trouble);
+	CHECK(Y.ndups > 300 && Y.nlates > 300, "duplicates %u late %u", Y.ndups,
+	      Y.nlates);
+	CHECK(Y.nroll > 300, "rollovers inside accepted batches %u", Y.nroll);
+	CHECK(Y.nnew > 300, "streams opened in accepted batches %u", Y.nnew);
+	CHECK(Y.nlong > 300, "streams across several waves %u", Y.nlong);
+	CHECK((Y.seen & all) == all, "seen %#x", Y.seen);
+	CHECK(Y.ncross == 0, "%u batches crossed 2^31 from ROC 0..3", Y.ncross);
+	/* the same worlds with about a third of the known streams at B - 2 .. B
+	 * for B = 2^16, 2^31 and 2^32, between streams at ROC 0..2 and the
+	 * ones the batches open: the segmented scan carries indices of 2^47
+	 * and small ones side by side.  2^16 is an ordinary rollover: the
+	 * shares of the run above hold (a quarter of the batches accepted, a
+	 * twentieth of that many rollovers).  At the others some batches cross
+	 * (declined, checked above), the others are accepted exactly */
+	for (b = 0; b < 3; b++) {
+		g_roc0 = BASE[b];
+		random_worlds(&W, 1500, &Z);
+		if (!b)
+			CHECK(Z.naccept > 375 && Z.nroll > 75 && !Z.ncross,
+			      "roc %#x: accepted %u rollovers %u crossed %u", g_roc0,
+			      Z.naccept, Z.nroll, Z.ncross);
+		else
+			CHECK(Z.naccept && Z.ncross, "roc %#x: accepted %u crossed "
+			      "%u", g_roc0, Z.naccept, Z.ncross);
+		printf("roc %#x: 1500 batches, %u taken, %u declined, %u crossed\n",
+		       g_roc0, Z.naccept, Z.nreject, Z.ncross);
+	}
+	printf("%u batches: %u accepted (%u must), %u rejected, %d wrong\n", 6000u,
+	       Y.naccept, Y.nmust, Y.nreject, g_bad);
 	return g_bad ? 1 : 0;
 }

@@ -10,7 +10,11 @@
  * session's arrivals network-shaped (loss, swaps, displacement, duplicates),
  * sequence numbers starting near 100, 32700 or 65000 (rollovers inside),
  * fresh and continuing states; some batches carry a session the rule must
- * leave unsettled.  Each batch runs twice:
+ * leave unsettled.  A second series starts the continuing sessions one and
+ * two rollovers below ROC 2^16, 2^31 and 2^32, beside fresh sessions at ROC
+ * 0: the reference's index is sign-extended from 2^31 on (misc.c:22-41, the
+ * sequential receiver here does the same), and a session that gets there
+ * must be left unsettled.  Each batch runs twice:
  *
  *   (a) grouped by session and scanned as the kernel does: EPT consecutive
  *       sorted positions per "thread", the threads' aggregates scanned with
@@ -429,6 +433,11 @@ static uint32_t network_shaped(uint32_t c, uint32_t *out, uint32_t cap,
 
 static const uint16_t S0[3] = {100, 32700, 65000};
 
+/* the continuing sessions' ROC: g_roc0 + 0..g_rocn-1; g_cross: the victim
+ * session continues at g_roc0 + 1 from 65000 and rolls over in the batch */
+static uint32_t g_roc0, g_rocn = 3;
+static int g_cross;
+
 /*
  * A batch.  unsettled 1: one session gets a copy of its top packet more
  * than K of its own arrivals after it, the arrivals between (copies of the
@@ -451,8 +460,8 @@ static void make_batch(struct batch *B, uint32_t K, int unsettled)
 		if (room > SEGMAX)
 			room = SEGMAX;
 		memset(st, 0, sizeof(*st));
-		if (l == victim && unsettled) {
-			if (unsettled == 2)
+		if (l == victim && (unsettled || g_cross)) {
+			if (unsettled == 2 || g_cross)
 				s0 = 65000;
 			c = 600 + rnd() % 100u;
 			if (c + K + 16 > room)
@@ -460,11 +469,13 @@ static void make_batch(struct batch *B, uint32_t K, int unsettled)
 		}
 		if (c > room)
 			c = room;
-		if (rnd() % 2u || (l == victim && unsettled == 2)) {
+		if (rnd() % 2u || (l == victim && (unsettled == 2 || g_cross))) {
 			/* continuing: `pre` packets up to s0 - 1 received */
 			const uint32_t pre = 1 + rnd() % 100u;
 			uint64_t ix;
-			st->roc = rnd() % 3u;
+			st->roc = g_roc0 + rnd() % g_rocn;
+			if (l == victim && g_cross)
+				st->roc = g_roc0 + 1;
 			for (k = 0; k < pre; k++)
 				ref_packet(st, (uint16_t)(s0 - pre + k), &ix);
 		}
@@ -529,7 +540,7 @@ int main(void)
 	static const uint32_t EPT[4] = {1, 2, 3, 4}, WV[3] = {2, 4, 8};
 	static const uint32_t KV[3] = {16, RX_LOOKBACK, 24};
 	static const uint32_t BLK[3] = {3, 8, 256};
-	uint32_t trial, nset = 0, nuns = 0, i, l;
+	uint32_t trial, nset = 0, nuns = 0, i, l, b;
 
 	for (trial = 0; trial < 400; trial++) {
 		const uint32_t K = KV[trial % 3u];
@@ -563,7 +574,49 @@ int main(void)
 	}
 	CHECK(nset >= 100 && nuns >= 50, "%u settled, %u unsettled batches: the "
 	      "traffic does not cover both", nset, nuns);
-	printf("%u batches settled, %u unsettled; %d wrong\n", nset, nuns,
-	       g_bad);
+	printf("%u batches settled, %u unsettled; ", nset, nuns);
+	/* continuing sessions at B - 2 and B - 1 for B = 2^16, 2^31, 2^32; in
+	 * every other batch the victim crosses B.  At 2^16 that is an
+	 * ordinary rollover: the traffic settles as often as above (a
+	 * quarter of the batches at least).  A session that crosses 2^31 or
+	 * 2^32, and one whose window is sign-extended already (every
+	 * continuing one below 2^32), must not settle */
+	for (b = 0; b < 3; b++) {
+		static const uint32_t BASE[3] = {0xfffeu, 0x7ffffffeu, 0xfffffffeu};
+		uint32_t ns2 = 0;
+		g_roc0 = BASE[b];
+		g_rocn = 2;
+		for (trial = 0; trial < 60; trial++) {
+			const uint32_t K = KV[trial % 3u];
+			const int tagged = (trial / 3u) % 2u;
+			const uint32_t ept = EPT[rnd() % 4u], W = WV[rnd() % 3u];
+			g_cross = trial % 2u;
+			make_batch(&B, K, 0);
+			run_kernel_shape(&B, ept, W, K, tagged, &Ra);
+			run_alone(&B, BLK[rnd() % 3u], K, tagged, &Rb);
+			CHECK(Ra.settled == Rb.settled, "roc %#x trial %u (ept %u W "
+			      "%u K %u): kernel shape settled %d, alone %d", g_roc0,
+			      trial, ept, W, K, Ra.settled, Rb.settled);
+			if (b && g_cross)
+				CHECK(!Rb.settled && !Ra.settled, "roc %#x trial %u: a "
+				      "session crossed and settled", g_roc0, trial);
+			if (!Ra.settled || !Rb.settled)
+				continue;
+			ns2++;
+			for (i = 0; i < B.n; i++)
+				CHECK(Ra.u[i] == Rb.u[i] && Ra.v[i] == Rb.v[i],
+				      "roc %#x trial %u packet %u: kernel shape "
+				      "%lld/%d, alone %lld/%d", g_roc0, trial, i,
+				      (long long)Ra.u[i], Ra.v[i], (long long)Rb.u[i],
+				      Rb.v[i]);
+			for (l = 0; l < B.ns; l++)
+				CHECK(same_state(&Ra.st1[l], &Rb.st1[l]), "roc %#x trial "
+				      "%u session %u: states differ", g_roc0, trial, l);
+		}
+		CHECK(b || ns2 >= 15, "roc %#x: %u of 60 batches settled", g_roc0,
+		      ns2);
+		printf("roc %#x: %u of 60 settled; ", g_roc0, ns2);
+	}
+	printf("%d wrong\n", g_bad);
 	return g_bad ? 1 : 0;
 }

@@ -33,6 +33,12 @@
  * u[] and mx[] from the serial recurrence and the same K, settles every
  * packet (a first step that is an ETIMEDOUT settles nothing).
  *
+ * The worlds run once with the known streams at ROC 0..2 and then with them
+ * at B - 2 .. B for B = 2^16, 2^31 and 2^32, beside the streams a batch opens
+ * at ROC 0.  The sequential receiver widens `int v` as misc.c:40 does, so the
+ * window's top is sign-extended from ROC 2^31 on; a batch in which a stream
+ * crosses 2^31 or 2^32 must be declined, every accepted one is exact.
+ *
  *   streams_rx_check            the random worlds
  *   streams_rx_check FILE       a recorded traffic (lines "B", then "ssrc seq"
  *                               per arrival; the table starts empty): per
@@ -160,7 +166,7 @@ static void sequential(const struct batch *B, struct tab *t, int *err,
 	for (i = 0; i < B->n; i++) {
 		const struct pkt *p = &B->p[i];
 		struct tseg_rec *st;
-		uint64_t lix, bm;
+		uint64_t lix, bm, ixf;
 		uint32_t s_l, v;
 		int diff;
 		ix[i] = 0;
@@ -181,10 +187,12 @@ static void sequential(const struct batch *B, struct tab *t, int *err,
 		lix = tseg_lix(*st);
 		bm = tseg_bitmap(*st);
 		v = ref_v(st->roc, s_l, p->seq);
-		ix[i] = (p->seq + (uint64_t)(int64_t)(int32_t)v * 65536ull) &
-			0xffffffffffffull;
+		/* misc.c:40: `int v` widened -- the window holds the
+		 * sign-extended index, the IV its low 48 bits */
+		ixf = p->seq + (uint64_t)(int64_t)(int32_t)v * 65536ull;
+		ix[i] = ixf & 0xffffffffffffull;
 		fl[i] = SD_RUN | SD_CIPHER;
-		if (!ref_replay_check(&lix, &bm, ix[i])) {
+		if (!ref_replay_check(&lix, &bm, ixf)) {
 			/* (the rollover above stays, s_l does not; the tag was
 			 * checked before: HMAC suites do not decrypt it) */
 			st->sl = s_l | TSEG_SL_SET;
@@ -516,6 +524,9 @@ static uint32_t ssrc_of(uint32_t k)
 enum { TR_NINTH = 1, TR_DUP = 2, TR_SWAP = 4, TR_JUMP = 8, TR_REPLAY = 16,
        TR_UNSET = 32, TR_GAP = 64, TR_FAR = 128 };
 
+/* the known streams' ROC: g_roc0 + 0..2 */
+static uint32_t g_roc0;
+
 static uint32_t make_world(struct world *W, uint32_t trouble_pm)
 {
 	struct tab *t = &W->t;
@@ -538,9 +549,11 @@ static uint32_t make_world(struct world *W, uint32_t trouble_pm)
 			done |= TR_UNSET;
 			continue;
 		}
-		r->roc = rnd() % 3;
+		r->roc = g_roc0 + rnd() % 3;
 		W->nxt[k] += 65536ull * r->roc;
-		lix = W->nxt[k] - 1;
+		/* the window's top as the reference leaves it (misc.c:40) */
+		lix = ((W->nxt[k] - 1) & 0xffffu) +
+		      (uint64_t)(int64_t)(int32_t)r->roc * 65536ull;
 		r->sl = (uint32_t)(lix & 0xffffu) | TSEG_SL_SET;
 		r->llo = (uint32_t)lix;
 		r->lhi = (uint32_t)(lix >> 32);
@@ -688,49 +701,58 @@ static int replay_file(const char *path)
 	return 0;
 }
 
-int main(int argc, char **argv)
-{
-	static struct world W;
-	const uint32_t all = TR_NINTH | TR_DUP | TR_SWAP | TR_JUMP | TR_REPLAY |
-			     TR_UNSET | TR_GAP | TR_FAR;
-	uint32_t it, naccept = 0, nreject = 0, nmust = 0, seen = 0, nroll = 0;
-	uint32_t ndups = 0, nlates = 0, nlong = 0, nacc_trouble = 0, nnew = 0;
-	uint32_t nshortk = 0;
+/* what a run of random batches met */
+struct tally {
+	uint32_t naccept, nreject, nmust, seen, nroll, ndups, nlates, nlong;
+	uint32_t nacc_trouble, nnew, nshortk, ncross;
+};
 
-	if (argc > 1)
-		return replay_file(argv[1]);
-	for (it = 0; it < 6000; it++) {
+/* nit batches from worlds whose known streams start at g_roc0 + 0..2 */
+static void random_batches(struct world *W, uint32_t nit, struct tally *Y)
+{
+	uint32_t it;
+	memset(Y, 0, sizeof(*Y));
+	for (it = 0; it < nit; it++) {
 		struct geo G;
 		const uint32_t pm = it % 8 < 2 ? 0 : it % 8 < 6 ? 60 : 300;
-		uint32_t tr, fail, i, k, nea = 0, ooo;
+		uint32_t tr, fail, i, k, nea = 0, ooo, cross = 0;
 		int must;
 
 		if (it % 4 == 0)
-			seen |= make_world(&W, pm);
+			Y->seen |= make_world(W, pm);
 		G.W = 1u << (1 + rnd() % 3);            /* 2 .. 8 */
 		G.B = G.W << (rnd() % 4);               /* .. 64, a power of two */
 		G.T = 1u << (rnd() % 5);                /* 1 .. 16 */
 		G.K = chance(500) ? RX_LOOKBACK : 2 + rnd() % 12;
-		tr = make_batch(&W, &g_B, chance(800) ? 400 : 40, pm);
+		tr = make_batch(W, &g_B, chance(800) ? 400 : 40, pm);
 		sequential(&g_B, &g_ts, g_err, g_ixs, g_fls);
 		memset(&g_P, 0, sizeof(g_P));
 		fail = planned(&g_B, G, &g_P);
 		must = must_accept(&g_B, G.K, g_err, &ooo);
-		nmust += (uint32_t)must;
-		seen |= tr;
-		CHECK(!(must && fail), "it %u: rejected (SPF %#x) a batch it must "
-		      "accept", it, fail);
-		CHECK(must || fail, "it %u: accepted a batch the sequential "
-		      "rx_settle does not settle", it);
+		Y->nmust += (uint32_t)must;
+		Y->seen |= tr;
+		CHECK(!(must && fail), "roc %#x it %u: rejected (SPF %#x) a batch it "
+		      "must accept", g_roc0, it, fail);
+		CHECK(must || fail, "roc %#x it %u: accepted a batch the sequential "
+		      "rx_settle does not settle", g_roc0, it);
+		/* a stream the receiver took across ROC 2^31 or 2^32: its index
+		 * is sign-extended from there on, the planner must decline */
+		for (k = 0; k < g_B.t0.n; k++) {
+			const uint32_t r0 = g_B.t0.st[k].roc, r1 = g_ts.st[k].roc;
+			cross |= (!(r0 >> 31) && (r1 >> 31)) || r1 < r0;
+		}
+		Y->ncross += cross;
+		CHECK(!cross || fail, "roc %#x it %u: accepted a batch that crosses "
+		      "2^31 or 2^32", g_roc0, it);
 		/* the next batch starts from what the receiver holds */
-		W.t = g_ts;
+		W->t = g_ts;
 		if (fail) {
-			nreject++;
+			Y->nreject++;
 			continue;
 		}
-		naccept++;
-		nacc_trouble += (tr & (TR_DUP | TR_SWAP | TR_REPLAY)) != 0;
-		nshortk += G.K < 14 && ooo;
+		Y->naccept++;
+		Y->nacc_trouble += (tr & (TR_DUP | TR_SWAP | TR_REPLAY)) != 0;
+		Y->nshortk += G.K < 14 && ooo;
 		for (i = 0; i < g_B.n; i++) {
 			CHECK(g_err[i] == 0 || g_err[i] == EALREADY, "it %u: "
 			      "accepted, packet %u has errno %d", it, i, g_err[i]);
@@ -745,11 +767,11 @@ int main(int argc, char **argv)
 		}
 		CHECK(g_P.ndup == nea, "it %u: %u duplicates counted, sequential "
 		      "%u", it, g_P.ndup, nea);
-		ndups += g_P.ndup;
-		nlates += g_P.nlate;
+		Y->ndups += g_P.ndup;
+		Y->nlates += g_P.nlate;
 		CHECK(g_P.t.n == g_ts.n, "it %u: %u streams, sequential %u", it,
 		      g_P.t.n, g_ts.n);
-		nnew += g_ts.n - g_B.t0.n;
+		Y->nnew += g_ts.n - g_B.t0.n;
 		for (k = 0; k < g_ts.n && k < g_P.t.n; k++) {
 			const struct tseg_rec *a = &g_P.t.st[k];
 			const struct tseg_rec *c = &g_ts.st[k];
@@ -761,25 +783,60 @@ int main(int argc, char **argv)
 			      a->llo, a->bhi, a->blo, c->ssrc, c->roc, c->sl,
 			      c->lhi, c->llo, c->bhi, c->blo);
 			if (k < g_B.t0.n && c->roc != g_B.t0.st[k].roc)
-				nroll++;
+				Y->nroll++;
 			for (i = 0; i < g_B.n; i++)
 				per += g_B.p[i].ssrc == c->ssrc;
-			nlong += per > 2 * G.B;
+			Y->nlong += per > 2 * G.B;
 		}
 	}
+}
+
+int main(int argc, char **argv)
+{
+	static struct world W;
+	static const uint32_t BASE[3] = {0xfffeu, 0x7ffffffeu, 0xfffffffeu};
+	const uint32_t all = TR_NINTH | TR_DUP | TR_SWAP | TR_JUMP | TR_REPLAY |
+			     TR_UNSET | TR_GAP | TR_FAR;
+	struct tally Y, Z;
+	uint32_t b;
+
+	if (argc > 1)
+		return replay_file(argv[1]);
+	random_batches(&W, 6000, &Y);
 	/* the run met what it is about */
-	CHECK(naccept > 1500 && nreject > 300, "accepted %u rejected %u", naccept,
-	      nreject);
-	CHECK(nacc_trouble > 300, "accepted batches with swaps, duplicates or "
-	      "replays %u", nacc_trouble);
-	CHECK(nshortk > 100, "accepted disturbed batches under a short look-back "
-	      "%u", nshortk);
-	CHECK(ndups > 300 && nlates > 300, "duplicates %u late %u", ndups, nlates);
-	CHECK(nroll > 300, "rollovers inside accepted batches %u", nroll);
-	CHECK(nnew > 300, "streams opened in accepted batches %u", nnew);
-	CHECK(nlong > 300, "streams longer than two workgroups %u", nlong);
-	CHECK((seen & all) == all, "seen %#x", seen);
-	printf("%u batches: %u accepted (%u must), %u rejected, %d wrong\n", it,
-	       naccept, nmust, nreject, g_bad);
+	CHECK(Y.naccept > 1500 && Y.nreject > 300, "accepted %u rejected %u",
+	      Y.naccept, Y.nreject);
+	CHECK(Y.nacc_trouble > 300, "accepted batches with swaps, duplicates or "
+	      "replays %u", Y.nacc_trouble);
+	CHECK(Y.nshortk > 100, "accepted disturbed batches under a short look-back "
+	      "%u", Y.nshortk);
+	CHECK(Y.ndups > 300 && Y.nlates > 300, "duplicates %u late %u", Y.ndups,
+	      Y.nlates);
+	CHECK(Y.nroll > 300, "rollovers inside accepted batches %u", Y.nroll);
+	CHECK(Y.nnew > 300, "streams opened in accepted batches %u", Y.nnew);
+	CHECK(Y.nlong > 300, "streams longer than two workgroups %u", Y.nlong);
+	CHECK((Y.seen & all) == all, "seen %#x", Y.seen);
+	CHECK(Y.ncross == 0, "%u batches crossed 2^31 from ROC 0..3", Y.ncross);
+	/* the same traffic with the known streams at B - 2 .. B for B = 2^16,
+	 * 2^31 and 2^32, beside the streams the batches open at ROC 0.  2^16 is
+	 * an ordinary rollover: the shares of the run above hold (a quarter
+	 * of the batches accepted, a twentieth with a rollover inside).  At
+	 * the others some batches cross (and are declined, checked above) and
+	 * some stay below or open new streams only (accepted, exactly) */
+	for (b = 0; b < 3; b++) {
+		g_roc0 = BASE[b];
+		random_batches(&W, 1500, &Z);
+		if (!b)
+			CHECK(Z.naccept > 375 && Z.nroll > 75 && !Z.ncross,
+			      "roc %#x: accepted %u rollovers %u crossed %u", g_roc0,
+			      Z.naccept, Z.nroll, Z.ncross);
+		else
+			CHECK(Z.naccept && Z.ncross, "roc %#x: accepted %u crossed "
+			      "%u", g_roc0, Z.naccept, Z.ncross);
+		printf("roc %#x: 1500 batches, %u taken, %u declined, %u crossed\n",
+		       g_roc0, Z.naccept, Z.nreject, Z.ncross);
+	}
+	printf("%u batches: %u accepted (%u must), %u rejected, %d wrong\n", 6000u,
+	       Y.naccept, Y.nmust, Y.nreject, g_bad);
 	return g_bad ? 1 : 0;
 }
