@@ -303,7 +303,10 @@ int srtp_alloc_many(struct srtp **srtpv, size_t n, enum srtp_suite suite,
  * "nosrxplan" (an unprotect batch of one session over several SSRCs whose
  * per-stream device plan was rejected for reordered or replayed packets
  * inside some stream goes straight to the host engine, not to the
- * per-stream receive planner),
+ * per-stream receive planner), "nosrplan" (an SRTCP batch of one session on
+ * device windows that carries several SSRCs, or whose one-stream plan was
+ * rejected for a second SSRC or a replayed or decreasing index, goes straight
+ * to the host engine, not to the one-session SRTCP planner),
  * "rxseq" (srtp_rx_index* and srtp_rx_fold walk
  * in one sequential pass, not in parallel parts), "freshmulti" (the
  * planner's first-batch hint: 1 sends a session's first batch to the
@@ -351,7 +354,17 @@ int srtp_gpu_tune(const char *name, long value);
  * with gaps, duplicated or replayed, completed by the per-stream receive
  * planner behind a rejected per-stream plan; "rxlate" and "rxdups" count its
  * packets too, "splans" does not move for them and "rejects" moves as
- * without it; srtp_gpu_tune "nosrxplan" sends them through the host engine).
+ * without it; srtp_gpu_tune "nosrxplan" sends them through the host engine),
+ * "srplans" (SRTCP batches of one session, protect or unprotect, over up to 8
+ * SSRCs in any arrival order -- interleaved, reordered, duplicated or replayed
+ * -- completed by the one-session SRTCP planner; "rxlate" and "rxdups" count
+ * its packets too; "rplans", "rejects", "folds", "devfolds", "mplans", "fused",
+ * "lplans" and "dplans" move as without it, so a one-stream session's batch
+ * keeps the one "rejects" of the in-order plan rejected in front of it;
+ * srtp_gpu_tune "nosrplan" sends them through the host engine), "srundos"
+ * (plans it accepted and undid on the device because a tag did not verify;
+ * the host engine then takes the batch and counts "misses" and "folds" as
+ * without the planner).
  * 0 for an unknown name.
  */
 uint64_t srtp_gpu_counter(const char *name);

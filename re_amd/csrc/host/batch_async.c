@@ -437,9 +437,20 @@ static int run_dev(int op, struct srtp **sessv, size_t nsess,
 			return r;
 	}
 	if ((op == OP_RTCP_ENC || op == OP_RTCP_DEC) && nsess == 1 &&
-	    !d->sess && sessv[0]->nstreams <= 1 &&
-	    !g_env.noplan && !g_env.general) {
-		int r = dev_planned_rtcp(op, sessv[0], d);
+	    !d->sess && !g_env.noplan && !g_env.general) {
+		/* one stream: the one-stream planner; several SSRCs (or a plan
+		 * rejected for a second one, or for a replayed or decreasing
+		 * index): the per-stream planner, exact in any arrival order */
+		int r = -1;
+		if (sessv[0]->nstreams <= 1) {
+			uint32_t pf = 0;
+			r = dev_planned_rtcp(op, sessv[0], d, &pf);
+			if (r == -1 && srp_eligible(pf))
+				r = dev_splanned_rtcp(op, sessv[0], d);
+		}
+		else if (!g_env.nosrplan) {
+			r = dev_splanned_rtcp(op, sessv[0], d);
+		}
 		if (r >= 0)
 			return r;
 	}

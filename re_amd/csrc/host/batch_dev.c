@@ -7,7 +7,8 @@
  * dev_planned picks among the three), reordered arrivals (plan_rx.hip),
  * several streams of one session (plan_streams.hip) and their reordered
  * arrivals (plan_streams_rx.hip, dev_srxplanned), SRTCP
- * (dev_planned_rtcp; many sessions with up to 8 SSRCs each:
+ * (dev_planned_rtcp; one session of several SSRCs or disturbed arrivals:
+ * plan_streams_rtcp.hip, dev_splanned_rtcp; many sessions with up to 8 SSRCs each:
  * plan_buckets_rtcp.hip, dev_mplanned_rtcp, and their reordered or replayed
  * arrivals: plan_buckets_rtcp_rx.hip, dev_mrrxplanned), many sessions with resident
  * state (dev_mplanned) and their reordered arrivals (plan_buckets_rx.hip,
@@ -1253,7 +1254,8 @@ static void rplan_apply(struct srtp *s, const struct sgpu_plan_out *po,
  * synchronisation.  -1: not plannable (nothing modified) or a forged
  * packet (undone), else 0 / errno.
  */
-static int dev_lplanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
+static int dev_lplanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d,
+			     uint32_t *pfail)
 {
 	const int prot = op == OP_RTCP_ENC;
 	const struct comp *c0 = &s->rtcp;
@@ -1331,6 +1333,7 @@ static int dev_lplanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 			fprintf(stderr, "re_srtp rtcp plan n=%zu %s: rejected "
 				"(SPF %#x)\n", n, prot ? "protect" : "unprotect",
 				po->fail);
+		*pfail = po->fail;
 		return -1;
 	}
 	count(&g_cnt_rplans, 1);
@@ -1360,10 +1363,12 @@ static int dev_lplanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
  * synchronisation.  -1: not plannable or a forged packet (undone), else 0
  * / errno.
  */
-int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
+int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d,
+		     uint32_t *pfail)
 {
+	*pfail = 0;
 	if (!g_env.noplanfuse)
-		return dev_lplanned_rtcp(op, s, d);
+		return dev_lplanned_rtcp(op, s, d, pfail);
 	const int prot = op == OP_RTCP_ENC;
 	const struct comp *c0 = &s->rtcp;
 	const int gcm = c0->mode == SGPU_MODE_GCM;
@@ -1433,6 +1438,7 @@ int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 	nfail = po->nfail;
 	if (po->fail) {
 		count(&g_cnt_rejects, 1);
+		*pfail = po->fail;
 		return -1;
 	}
 	count(&g_cnt_rplans, 1);
@@ -1452,6 +1458,167 @@ int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 		s->nstreams = ns0;
 	}
 	return err;
+}
+
+/* ---- SRTCP, one session, several SSRCs or disturbed arrivals ------------ */
+/* (plan_streams_rtcp.hip) */
+
+/* a rejected one-stream SRTCP plan the per-stream planner may take: only a
+ * second SSRC (or one other than the known stream's) or a replayed or
+ * decreasing index was in its way */
+int srp_eligible(uint32_t pfail)
+{
+	return !g_env.nosrplan && pfail &&
+	       !(pfail & ~(uint32_t)(SPF_SSRC | SPF_REPLAY));
+}
+
+/*
+ * One-session SRTCP protect / unprotect batch over up to SRTP_MAX_STREAMS
+ * SSRCs in any arrival order: the RTCP parse prologue (with the E || index
+ * words for unprotect), sgpu_splan_rtcp, the general descriptor-driven crypto
+ * launch (class 2, GCM 0) guarded by its verdict, the guarded results, one
+ * copy back, one synchronisation; then the streams the batch opened are
+ * appended in first-appearance order and every touched stream takes its
+ * rtcp_index (protect) or replay window (unprotect, HMAC suites) after the
+ * batch.  0: done; -1: declined (a 9th SSRC, a copy older than the look-back,
+ * any other failed check, an imported window beyond 31 bits), or a forged
+ * packet (undone) -- nothing modified, nothing counted but srundos, the
+ * caller's fallback continues; errno.
+ */
+int dev_splanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
+{
+	const int prot = op == OP_RTCP_ENC;
+	const struct comp *c0 = &s->rtcp;
+	const int gcm = c0->mode == SGPU_MODE_GCM;
+	const int rxh = !prot && c0->has_hmac;
+	const size_t n = d->n;
+	const uint32_t grow = 4u + c0->tag_len + (gcm ? 16u : 0u);
+	const int32_t delta = prot ? (int32_t)grow : -(int32_t)grow;
+	const size_t scr = sgpu_splan_rtcp_scratch((uint32_t)n);
+	/* hd: the parsed headers | the E || index words */
+	const struct ws_sizes z = {
+		.hd = n * (sizeof(struct sgpu_hdr) + 12), .dsc = n * 8,
+		.vs = n * 5 + 64, .cm = 4,
+		.pl = 64 + sizeof(struct sgpu_srplan_out), .es = n * 4};
+	struct ws_layout L;
+	struct sgpu_compact C;
+	struct sgpu_srplan_in in;
+	struct sgpu_srplan_out *ro, *ro_d;
+	uint32_t *eix_d;
+	void *stream = d->stream;
+	struct ws *w = ws_get();
+	unsigned k;
+	int err;
+
+	if (!w)
+		return ENOMEM;
+	if (s->nstreams > SRTP_MAX_STREAMS)
+		return -1;
+	/* the records hold 32 bits of the window's top (an imported one may
+	 * lie higher: the host's replay_check takes it) */
+	if (rxh)
+		for (k = 0; k < s->nstreams; k++)
+			if (s->streams[k].replay_rtcp.lix > 0x7fffffffu)
+				return -1;
+	err = ws_layout_reserve(w, n, &z, &L);
+	if (!err)
+		err = pool_reserve(w, &w->mscr, scr);
+	if (err)
+		return err;
+	eix_d = (uint32_t *)(w->hd.d + n * sizeof(struct sgpu_hdr));
+	ro = (struct sgpu_srplan_out *)w->pl.h;
+	ro_d = (struct sgpu_srplan_out *)w->pl.d;
+
+	memset(&in, 0, sizeof(in));
+	rplan_in(&in.c, s, (uint32_t)n, prot);
+	in.nst = s->nstreams;
+	in.lookback = RX_LOOKBACK;
+	in.zeroed = 1;
+	for (k = 0; k < s->nstreams; k++) {
+		const struct srtp_stream *x = &s->streams[k];
+		in.st[k].ssrc = x->ssrc;
+		in.st[k].ix = prot ? x->rtcp_index : (uint32_t)x->replay_rtcp.lix;
+		in.st[k].blo = (uint32_t)x->replay_rtcp.bitmap;
+		in.st[k].bhi = (uint32_t)(x->replay_rtcp.bitmap >> 32);
+	}
+	{
+		/* one launch: parse (+ E || index words) + end copy + zeroed
+		 * plan out + comp map */
+		struct sgpu_prologue pro = {
+			.end_copy = L.es, .z0 = (uint32_t *)ro_d,
+			.nz0 = (uint32_t)(sizeof(*ro) / 4), .cm_out = L.cm,
+			.cm = c0->dev};
+		err = sgpu_parse_prologue(d->arena, d->arena_size, d->pos,
+					  d->end, L.hdr, prot ? NULL : eix_d,
+					  (uint32_t)n, 1, &pro, stream);
+	}
+	if (!err)
+		err = sgpu_splan_rtcp(&in, L.hdr, prot ? NULL : eix_d, d->pos,
+				      L.es, d->cap, d->arena_size, L.desc,
+				      w->mscr.d, scr, ro_d, stream);
+	/* the general kernel's SRTCP form: E per packet from desc (an
+	 * EALREADY packet: MAC only) */
+	C = compact_of(d, &L);
+	C.nfail = &ro_d->tab.base.nfail;
+	C.uniform = 1;
+	C.guard = &ro_d->tab.base.fail;
+	C.rtcp = 1;
+	if (!err)
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, gcm ? 0 : 2, prot, stream);
+	if (!err)
+		err = sgpu_splan_rtcp_commit(&in, ro_d, w->mscr.d, L.es, d->end,
+					     d->err, delta, stream);
+	if (!err)
+		err = sgpu_memcpy_d2h(ro, ro_d, sizeof(*ro), stream);
+	if (!err)
+		err = sgpu_stream_sync(stream);
+	if (err)
+		return err;
+	if (ro->tab.base.fail) {
+		if (g_env.times)
+			fprintf(stderr, "re_srtp rtcp streams plan n=%zu %s: "
+				"declined (SPF %#x)\n", n,
+				prot ? "protect" : "unprotect", ro->tab.base.fail);
+		return -1;
+	}
+	if (ro->tab.base.nfail) {
+		/* a forged packet: undo on the device (the results were not
+		 * written), fold on the host engine -- which counts the misses
+		 * and the one fold, as it does without this planner */
+		count(&g_cnt_srundos, 1);
+		C.undo = 1;
+		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				       (int)c0->nr, gcm ? 0 : 2, 0, stream);
+		if (!err)
+			err = sgpu_stream_sync(stream);
+		return err ? err : -1;
+	}
+	/* new SSRCs in first-appearance order (stream_new, stream.c:45-67),
+	 * then every touched stream's state after the batch */
+	for (k = 0; k < ro->tab.nst && k < SRTP_MAX_STREAMS; k++) {
+		struct srtp_stream *x = &s->streams[k];
+		const struct sgpu_rtcp_rec *a = &ro->after[k];
+		if (k >= s->nstreams) {
+			memset(x, 0, sizeof(*x));
+			x->ssrc = ro->tab.ssrc[k];
+		}
+		if (!ro->cnt[k])
+			continue;
+		if (prot) {
+			x->rtcp_index = a->ix;
+		}
+		else if (rxh) {
+			x->replay_rtcp.lix = a->ix;
+			x->replay_rtcp.bitmap = (uint64_t)a->bhi << 32 | a->blo;
+		}
+	}
+	if (ro->tab.nst > s->nstreams)
+		s->nstreams = ro->tab.nst;
+	count(&g_cnt_srplans, 1);
+	count(&g_cnt_rxlate, ro->nlate);
+	count(&g_cnt_rxdups, ro->ndup);
+	return 0;
 }
 
 /* ---- SRTCP, many sessions with up to 8 SSRCs each ---------------------- */

@@ -147,6 +147,12 @@ uint64_t g_cnt_srxplans; /* reordered / duplicated one-session unprotect
 				   per-stream receive planner
 				   (plan_streams_rx.hip); rxlate and rxdups count
 				   its packets too */
+uint64_t g_cnt_srplans;  /* one-session SRTCP batches over several SSRCs or
+				   in disturbed order completed by the per-stream
+				   planner (plan_streams_rtcp.hip); rxlate and
+				   rxdups count its packets too */
+uint64_t g_cnt_srundos;  /* ... plans it accepted and undid for a forged
+				   packet (the host engine then takes the batch) */
 uint64_t g_cnt_rxplans;  /* reordered / duplicated one-stream unprotect
 				   batches completed by the receive planner
 				   (plan_rx.hip) */
@@ -236,6 +242,10 @@ uint64_t srtp_gpu_counter(const char *name)
 		return __atomic_load_n(&g_cnt_msrxplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "srxplans"))
 		return __atomic_load_n(&g_cnt_srxplans, __ATOMIC_RELAXED);
+	if (!strcmp(name, "srplans"))
+		return __atomic_load_n(&g_cnt_srplans, __ATOMIC_RELAXED);
+	if (!strcmp(name, "srundos"))
+		return __atomic_load_n(&g_cnt_srundos, __ATOMIC_RELAXED);
 	if (!strcmp(name, "lbtimeouts"))
 		return __atomic_load_n(&g_cnt_lbtimeout, __ATOMIC_RELAXED);
 	if (!strcmp(name, "pcbatches"))
@@ -341,6 +351,8 @@ int srtp_gpu_tune(const char *name, long value)
 		g_env.nomsrxplan = value > 0;
 	else if (!strcmp(name, "nosrxplan"))
 		g_env.nosrxplan = value > 0;
+	else if (!strcmp(name, "nosrplan"))
+		g_env.nosrplan = value > 0;
 	else if (!strcmp(name, "rxseq"))
 		g_env.rxseq = value > 0;
 	else if (!strcmp(name, "freshmulti"))

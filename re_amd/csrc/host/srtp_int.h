@@ -143,6 +143,12 @@ struct srtp_env {
 				   packets goes straight to the host engine,
 				   not to the receive planner of
 				   plan_streams_rx.hip */
+	int nosrplan;           /* srtp_gpu_tune nosrplan: a one-session SRTCP
+				   batch over several SSRCs, or whose one-stream
+				   plan was rejected for a second SSRC or a
+				   replayed index, goes straight to the host
+				   engine, not to the planner of
+				   plan_streams_rtcp.hip */
 	int nomrplan;           /* srtp_gpu_tune nomrplan: many-session SRTCP
 				   batches on device windows go through the
 				   host engine (dev_staged), not the bucket
@@ -311,7 +317,7 @@ extern uint64_t g_cnt_splans, g_cnt_fused, g_cnt_gated;
 extern uint64_t g_cnt_dplans, g_cnt_mplans, g_cnt_rplans, g_cnt_lbtimeout;
 extern uint64_t g_cnt_lplans, g_cnt_mrplans, g_cnt_msplans, g_cnt_msrxplans;
 extern uint64_t g_cnt_rxplans, g_cnt_rxlate, g_cnt_rxdups, g_cnt_mrxplans;
-extern uint64_t g_cnt_mrrxplans, g_cnt_srxplans;
+extern uint64_t g_cnt_mrrxplans, g_cnt_srxplans, g_cnt_srplans, g_cnt_srundos;
 extern int g_fresh_multi;       /* srtp.c: the last first batch of a session
 				   showed several SSRCs (see there) */
 extern __thread struct tk_owner *t_own; /* srtp.c: this thread's async
@@ -531,7 +537,10 @@ int dev_splanned(int op, struct srtp *s, struct srtp_batch_dev *d,
 int srx_eligible(int op, size_t nsess, const struct srtp_batch_dev *d,
 		 uint32_t pfail);
 int dev_srxplanned(struct srtp *s, struct srtp_batch_dev *d);
-int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d);
+int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d,
+		     uint32_t *pfail);
+int srp_eligible(uint32_t pfail);
+int dev_splanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d);
 int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 		      struct srtp_batch_dev *d, uint32_t *pfail);
 int mrrx_eligible(int op, const struct srtp *s, uint32_t pfail);

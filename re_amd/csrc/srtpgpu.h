@@ -1040,6 +1040,66 @@ int   sgpu_splan_rx_commit(const struct sgpu_srxplan_out *out,
 			   const uint32_t *es, uint32_t *pos, uint32_t *end,
 			   int32_t *err, uint32_t n, uint32_t tag, void *stream);
 
+/*
+ * Exact device plan of a single-session SRTCP batch, protect or unprotect,
+ * over up to SGPU_SP_MAX SSRCs, in any arrival order (plan_streams_rtcp.hip;
+ * the rule per stream: hip/plan_rtcp_seg.h and hip/plan_rtcp_seg_rx.h, composed
+ * by hip/plan_rtcp_str.h) -- what sgpu_plan_rtcp rejects with SPF_SSRC /
+ * SPF_REPLAY.  hdr / eix: the RTCP parse (eix: unprotect; NULL for protect).
+ * The stream table is sgpu_splan_table's (RTP and RTCP share it); the packets
+ * are partitioned stably by slot.  Protect: a packet's rank in its stream
+ * numbers it.  Unprotect, GCM: no replay window, every packet stands alone.
+ * Unprotect, HMAC suites: the index travels in the packet, one segmented
+ * (sum, max) scan gives every arrival's index and the maximum before it, and
+ * rx_replay with tags verified behind it is the whole rule; an arrival it
+ * cannot settle within in->lookback: SPF_REPLAY.  out->tab.base.fail != 0: not
+ * taken, nothing modified.  fail guards the crypto launch (class 2, GCM 0),
+ * which counts its tag misses in out->tab.base.nfail; sgpu_splan_rtcp_commit
+ * behind it writes the caller's end / err (0 or EALREADY) unless fail or
+ * nfail.  Every launch is bounded by its own grid: no workgroup waits for
+ * another.
+ */
+struct sgpu_srplan_in {
+	struct sgpu_rplan_in c;         /* n, prot, tag, gcm, hmac, encrypted,
+					   need, maxlen */
+	uint32_t nst;           /* streams before the batch */
+	uint32_t lookback;      /* in-stream arrivals searched for a
+				   duplicate's original (RX_LOOKBACK) */
+	uint32_t zeroed;        /* out already zeroed */
+	uint32_t pad;
+	struct sgpu_rtcp_rec st[SGPU_SP_MAX];   /* ix: rtcp_index (protect),
+						   replay_rtcp.lix (unprotect) */
+};
+
+struct sgpu_srplan_out {
+	struct sgpu_splan_out tab;      /* base.fail / nfail, nst, ssrc[]: the
+					   table after the batch */
+	uint32_t nlate;         /* packets accepted below their window's top */
+	uint32_t ndup;          /* EALREADY verdicts */
+	uint32_t cnt[SGPU_SP_MAX];      /* packets per slot */
+	uint32_t start[SGPU_SP_MAX];    /* the slot's run in stream-major order */
+	uint64_t bits[SGPU_SP_MAX];     /* accepted packets' window bits */
+	struct sgpu_rtcp_rec after[SGPU_SP_MAX];        /* touched slots
+							   (cnt != 0): the record
+							   after the batch */
+};
+
+unsigned sgpu_splan_rtcp_block(void);   /* packets per workgroup */
+size_t sgpu_splan_rtcp_scratch(uint32_t n);
+int   sgpu_splan_rtcp(const struct sgpu_srplan_in *in,
+		      const struct sgpu_hdr *hdr, const uint32_t *eix,
+		      const uint32_t *pos, const uint32_t *end,
+		      const uint32_t *cap, uint64_t arena_size, uint64_t *desc,
+		      void *scratch, size_t scratch_bytes,
+		      struct sgpu_srplan_out *out, void *stream);
+/* es: the ends before the call; end / err: the caller's arrays; delta: the
+ * end change of a processed packet */
+int   sgpu_splan_rtcp_commit(const struct sgpu_srplan_in *in,
+			     const struct sgpu_srplan_out *out,
+			     const void *scratch, const uint32_t *es,
+			     uint32_t *end, int32_t *err, int32_t delta,
+			     void *stream);
+
 int   sgpu_plan_rtcp(const struct sgpu_rplan_in *in,
 		     const struct sgpu_hdr *hdr, const uint32_t *eix,
 		     const uint32_t *pos, const uint32_t *end,

@@ -602,14 +602,16 @@ def batch_wait(ticket):
 
 def counter(name):
     """srtp_gpu_counter: "misses", "folds", "rejects", the planners'
-    ("mrplans", "mrrxplans", "msplans", "msrxplans", "rxlate", "rxdups", ...)
-    since load; 0 for a name the library does not know"""
+    ("mrplans", "mrrxplans", "msplans", "msrxplans", "srplans", "srundos",
+    "rxlate", "rxdups", ...) since load; 0 for a name the library does not
+    know"""
     return int(lib().srtp_gpu_counter(name.encode()))
 
 
 class tune:
     """srtp_gpu_tune as a context manager: with tune(general=1): ...
-    (knobs restored to their defaults on exit)"""
+    (knobs restored to their defaults on exit; "nosrplan", "nosrxplan",
+    "nomrplan", ...: include/re_srtp_batch.h)"""
 
     def __init__(self, **knobs):
         self.knobs = knobs
