@@ -49,8 +49,9 @@ static __thread int t_naws;
 
 static int run_dev(int op, struct srtp **sessv, size_t nsess,
 		   struct srtp_batch_dev *d);
-static int dev_staged(int op, struct srtp **sessv, size_t nsess,
-		      struct srtp_batch_dev *d);
+static int after_host(int op, struct srtp **sessv, size_t nsess,
+		      struct srtp_batch_dev *d, int tried, int radix,
+		      uint32_t pfail);
 
 /* complete the thread's oldest pending call (its result stays in the
  * ticket until srtp_batch_wait) */
@@ -89,34 +90,9 @@ static void tk_finish_one(void)
 	}
 	if (r == -1) {
 		r = sess_host(k->sessv, k->nsess);
-		/* a second SSRC in a single-stream plan: the per-stream one */
-		if (!r && t->kind == TK_PLANNED && (k->pfail & SPF_SSRC)) {
-			uint32_t pf = 0;
-			r = dev_splanned(k->op, k->sessv[0], &k->d, &pf);
-			if (r == -1 && srx_eligible(k->op, k->nsess, &k->d, pf))
-				r = dev_srxplanned(k->sessv[0], &k->d);
-		}
-		/* reordered or replayed arrivals inside some stream of a
-		 * per-stream plan: its receive planner */
-		else if (!r && t->kind == TK_SPLANNED &&
-			 srx_eligible(k->op, k->nsess, &k->d, k->pfail))
-			r = dev_srxplanned(k->sessv[0], &k->d);
-		/* a session over the counting grouping's bound: the radix
-		 * sort */
-		else if (!r && t->kind == TK_MPLANNED && (k->pfail & SPF_SEG) &&
-			 !k->radix) {
-			uint32_t pf = 0;
-			r = dev_mplanned_(k->op, k->sessv, k->nsess, &k->d, 1,
-					  &pf);
-		}
-		/* reordered or replayed arrivals: the receive planner */
-		else if (!r && t->kind == TK_PLANNED &&
-			 rx_eligible(k->op, k->sessv[0], k->pfail))
-			r = dev_rxplanned(k->sessv[0], &k->d, NULL, NULL, NULL);
-		else if (!r)
-			r = -1;
-		if (r == -1)
-			r = dev_staged(k->op, k->sessv, k->nsess, &k->d);
+		if (!r)
+			r = after_host(k->op, k->sessv, k->nsess, &k->d, t->kind,
+				       k->radix, k->pfail);
 	}
 	t->result = r;
 	t->kind = TK_DONE;
@@ -365,46 +341,36 @@ static int dev_staged(int op, struct srtp **sessv, size_t nsess,
 	return err;
 }
 
-static int run_dev(int op, struct srtp **sessv, size_t nsess,
-		   struct srtp_batch_dev *d)
+/*
+ * The ladder behind sess_host(), for the synchronous calls (run_dev) and for
+ * a queued call whose plan came back rejected (tk_finish_one), so that both
+ * reach the same planners.  tried: the planner whose plan is in already
+ * (TK_PLANNED, TK_SPLANNED, TK_MPLANNED; 0: none, or a many-session one
+ * through dev_mplanned); radix: that plan grouped by the radix sort; pfail:
+ * why it left (SPF_* bits, MPF_MULTI from the gather; 0: no plan tried, or a
+ * forged packet the host must fold).
+ */
+static int after_host(int op, struct srtp **sessv, size_t nsess,
+		      struct srtp_batch_dev *d, int tried, int radix,
+		      uint32_t pfail)
 {
-	size_t k;
-	uint32_t mpf = 0;       /* why the bucket planner left a batch */
-	if (!sessv || !nsess || !d || !d->arena || !d->pos || !d->end ||
-	    !d->cap || !d->err)
-		return EINVAL;
-	for (k = 0; k < nsess; k++)
-		if (!sessv[k])
-			return EINVAL;
-	if (d->n == 0)
-		return 0;
-	if (d->n > UINT32_MAX / 4 || d->arena_size > UINT32_MAX)
-		return EINVAL;
-	/* many sessions: planned on the device against the resident states */
-	if ((op == OP_RTP_ENC || op == OP_RTP_DEC) && nsess > 1 && d->sess &&
-	    !g_env.noplan && !g_env.general) {
+	/* a queued many-session plan with a session over the counting
+	 * grouping's bound: the radix sort (dev_mplanned's second try, which a
+	 * synchronous call makes on the resident states) */
+	if (tried == TK_MPLANNED && (pfail & SPF_SEG) && !radix) {
 		uint32_t pf = 0;
-		int r = dev_mplanned(op, sessv, nsess, d, &pf);
-		/* reordered or replayed arrivals inside some session: the bucket
-		 * receive planner, the states staying resident */
-		if (r == -1 && mrx_eligible(op, nsess, pf))
-			r = dev_mrxplanned(sessv, nsess, d);
-		if (r >= 0)
+		int r = dev_mplanned_(op, sessv, nsess, d, 1, &pf);
+		if (r != -1)
 			return r;
-		if (r == -1)
-			mpf = pf;
-	}
-	{
-		int err = sess_host(sessv, nsess);
-		if (err)
-			return err;
+		pfail = pf;
 	}
 	/* sessions that hold, or gain in this batch, several SSRCs, each
 	 * stream in order: the multi-SSRC bucket planner over the host's
 	 * stream tables (current after sess_host) */
-	if (mpf && ms_eligible(op, nsess, mpf)) {
+	if (pfail && ms_eligible(op, nsess, pfail)) {
 		uint32_t pf = 0;
-		int r = dev_msplanned(op, sessv, nsess, d, mpf != MPF_MULTI, &pf);
+		int r = dev_msplanned(op, sessv, nsess, d, pfail != MPF_MULTI,
+				      &pf);
 		/* reordered or replayed arrivals inside some stream: the receive
 		 * planner on the tables that plan uploaded */
 		if (r == -1 && msrx_eligible(op, pf))
@@ -419,11 +385,18 @@ static int run_dev(int op, struct srtp **sessv, size_t nsess,
 		 * the per-stream planner */
 		uint32_t pf = SPF_SSRC;
 		int r = -1;
-		if (sessv[0]->nstreams <= 1 && !g_env.splan &&
-		    (sessv[0]->nstreams ||
-		     !__atomic_load_n(&g_fresh_multi, __ATOMIC_RELAXED)))
+		if (tried)
+			pf = pfail;
+		else if (sessv[0]->nstreams <= 1 && !g_env.splan &&
+			 (sessv[0]->nstreams ||
+			  !__atomic_load_n(&g_fresh_multi, __ATOMIC_RELAXED)))
 			r = dev_planned(op, sessv[0], d, &pf);
-		if (r == -1 && (pf & SPF_SSRC)) {
+		if (tried == TK_SPLANNED) {
+			/* the per-stream plan is in: its receive planner */
+			if (srx_eligible(op, nsess, d, pf))
+				r = dev_srxplanned(sessv[0], d);
+		}
+		else if (r == -1 && (pf & SPF_SSRC)) {
 			r = dev_splanned(op, sessv[0], d, &pf);
 			/* reordered or replayed arrivals inside some stream: the
 			 * per-stream receive planner */
@@ -468,6 +441,43 @@ static int run_dev(int op, struct srtp **sessv, size_t nsess,
 			return r;
 	}
 	return dev_staged(op, sessv, nsess, d);
+}
+
+static int run_dev(int op, struct srtp **sessv, size_t nsess,
+		   struct srtp_batch_dev *d)
+{
+	size_t k;
+	uint32_t mpf = 0;       /* why the bucket planner left a batch */
+	if (!sessv || !nsess || !d || !d->arena || !d->pos || !d->end ||
+	    !d->cap || !d->err)
+		return EINVAL;
+	for (k = 0; k < nsess; k++)
+		if (!sessv[k])
+			return EINVAL;
+	if (d->n == 0)
+		return 0;
+	if (d->n > UINT32_MAX / 4 || d->arena_size > UINT32_MAX)
+		return EINVAL;
+	/* many sessions: planned on the device against the resident states */
+	if ((op == OP_RTP_ENC || op == OP_RTP_DEC) && nsess > 1 && d->sess &&
+	    !g_env.noplan && !g_env.general) {
+		uint32_t pf = 0;
+		int r = dev_mplanned(op, sessv, nsess, d, &pf);
+		/* reordered or replayed arrivals inside some session: the bucket
+		 * receive planner, the states staying resident */
+		if (r == -1 && mrx_eligible(op, nsess, pf))
+			r = dev_mrxplanned(sessv, nsess, d);
+		if (r >= 0)
+			return r;
+		if (r == -1)
+			mpf = pf;
+	}
+	{
+		int err = sess_host(sessv, nsess);
+		if (err)
+			return err;
+	}
+	return after_host(op, sessv, nsess, d, 0, 0, mpf);
 }
 
 enum { HOSTW = 0, DEV = 1 };
