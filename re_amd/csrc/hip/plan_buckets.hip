@@ -930,11 +930,6 @@ k_bp_finish(const struct sgpu_bplan P)
 
 /* ---- host side ------------------------------------------------------ */
 
-static size_t bp_align(size_t x)
-{
-	return (x + 255) & ~(size_t)255;
-}
-
 /* srtp_gpu_tune bpexp (A/B): the expected entries per bucket the
  * geometry aims at instead of SGPU_BP_EXP (0: the default) */
 static uint32_t g_bp_exp;
@@ -975,17 +970,6 @@ extern "C" int sgpu_bplan_geometry(uint32_t n, uint32_t nsess,
 		return 0;
 	}
 	return -1;
-}
-
-extern "C" size_t sgpu_bplan_scratch(uint32_t n, uint32_t nsess, uint32_t nb,
-				     uint32_t cap)
-{
-	const size_t na = (n + BPB * SGPU_BP_PPT - 1) / (BPB * SGPU_BP_PPT);
-	return bp_align((size_t)nb * cap * 16) +    /* tmp */
-	       bp_align((size_t)nb * cap * 4) +     /* sorted */
-	       bp_align(na * 4) +                    /* afail */
-	       bp_align((size_t)nsess * 4) +         /* sseg */
-	       bp_align((size_t)nsess * 32);         /* sout */
 }
 
 static int bp_check(const struct sgpu_bplan *b)

@@ -1,25 +1,37 @@
 /*
  * batch_dev.c -- fully device-resident batches (srtp_*_batch_dev):
  * packets, positions and stream state stay in HBM and the plan runs on the
- * device -- one stream planned inside the crypto launch or by the
- * one-launch planner in front of it (k_ctr_fused.h, fz_issue / fz_finish),
- * one stream by the separate planner kernels (dp_issue / dp_finish;
- * dev_planned picks among the three), reordered arrivals (plan_rx.hip),
- * several streams of one session (plan_streams.hip) and their reordered
- * arrivals (plan_streams_rx.hip, dev_srxplanned), SRTCP
- * (dev_planned_rtcp; one session of several SSRCs or disturbed arrivals:
- * plan_streams_rtcp.hip, dev_splanned_rtcp; many sessions with up to 8 SSRCs each:
- * plan_buckets_rtcp.hip, dev_mplanned_rtcp, and their reordered or replayed
- * arrivals: plan_buckets_rtcp_rx.hip, dev_mrrxplanned), many sessions with resident
- * state (dev_mplanned) and their reordered arrivals (plan_buckets_rx.hip,
- * dev_mrxplanned), many sessions with up to 8 SSRCs each
- * (plan_buckets_rtp_streams.hip, dev_msplanned) and their reordered
- * arrivals (plan_buckets_rtp_streams_rx.hip, dev_msrxplanned).  Each call
- * of the others is a struct dcall between its launches
- * (*_issue) and its completion (*_finish), so the synchronous calls
- * (dev_call) and the asynchronous tickets (batch_async.c) share it.  Where a
- * call's arrays lie in the workspace pools: struct ws_layout (srtp_int.h)
- * and, for w->fz, struct fz_layout.  Split out of srtp.c.
+ * device.  The routes (batch_async.c after_host / run_dev pick among them):
+ *
+ * route              planner                          state     call
+ * RTP, one session
+ *  fz_issue/_finish  k_ctr_fused.h (in or before the  host      issue/finish
+ *                    crypto launch)
+ *  dp_issue/_finish  srtp_kernels.hip k_plan_*        host      issue/finish
+ *  dev_rxplanned     plan_rx.hip                      host      sync only
+ *  dev_splanned      plan_streams.hip                 host      issue/finish
+ *  dev_srxplanned    plan_streams_rx.hip              host      sync only
+ * RTP, many sessions
+ *  dev_mplanned      plan_buckets.hip, plan_multi.hip resident  issue/finish
+ *  dev_mrxplanned    plan_buckets_rx.hip              resident  sync only
+ *  dev_msplanned     plan_buckets_rtp_streams.hip     table     sync only
+ *  dev_msrxplanned   plan_buckets_rtp_streams_rx.hip  table     sync only
+ * SRTCP, one session
+ *  dev_planned_rtcp  srtp_kernels.hip (k_rp_plan,     host      sync only
+ *                    k_plan_rtcp)
+ *  dev_splanned_rtcp plan_streams_rtcp.hip            host      sync only
+ * SRTCP, many sessions
+ *  dev_mplanned_rtcp plan_buckets_rtcp.hip            table     sync only
+ *  dev_mrrxplanned   plan_buckets_rtcp_rx.hip         table     sync only
+ *
+ * state: where the plan reads the stream states -- host: passed in with the
+ * launch; resident: the table in HBM (sgpu_sst_*); table: the host's stream
+ * tables, uploaded by the call (struct tab_layout).  call: an issue/finish
+ * route is a struct dcall between its launches (*_issue) and its completion
+ * (*_finish), so the synchronous calls (dev_call) and the asynchronous
+ * tickets (batch_async.c) share it; a sync-only route synchronises itself.
+ * Where a call's arrays lie in the workspace pools: struct ws_layout
+ * (srtp_int.h), struct fz_layout for w->fz, bp_layout.h for w->bp.
  */
 #include <errno.h>
 #include <pthread.h>
@@ -35,6 +47,7 @@
 #include "re_rtcp_batch.h"
 #include "../srtpgpu.h"
 #include "../hip/plan_rx_rule.h"
+#include "bp_layout.h"
 #include "fault.h"
 #include "pool.h"
 #include "srtp_int.h"
@@ -84,6 +97,43 @@ static int undone(int err, const struct srtp_batch_dev *d, const uint32_t *es)
 	if (!err)
 		err = sgpu_stream_sync(d->stream);
 	return err ? err : -1;
+}
+
+/* the same behind a plan that wrote no result (its commit or finish launch
+ * is guarded by the miss count): the ends never moved */
+static int undo_synced(int err, void *stream)
+{
+	if (!err)
+		err = sgpu_stream_sync(stream);
+	return err ? err : -1;
+}
+
+/* an SRTCP call's undo launch: its crypto launch C again over the one class
+ * SRTCP has (AES-CM: 2, the cipher region starts at byte 8; GCM: 0) */
+static int undo_rtcp(const struct srtp_batch_dev *d, struct sgpu_compact C,
+		     const struct comp *c0)
+{
+	C.undo = 1;
+	return sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
+				(int)c0->nr, c0->mode == SGPU_MODE_GCM ? 0 : 2, 0,
+				d->stream);
+}
+
+/* the streams a batch opened, appended in first-appearance order
+ * (stream_new, stream.c:45-67); returns the slots of the table after the
+ * batch, of which the caller advances the touched ones */
+static unsigned streams_append(struct srtp *s, const struct sgpu_splan_out *tab)
+{
+	const unsigned nst = tab->nst < SRTP_MAX_STREAMS ? tab->nst
+							  : SRTP_MAX_STREAMS;
+	unsigned k;
+	for (k = s->nstreams; k < nst; k++) {
+		memset(&s->streams[k], 0, sizeof(s->streams[k]));
+		s->streams[k].ssrc = tab->ssrc[k];
+	}
+	if (tab->nst > s->nstreams)
+		s->nstreams = tab->nst;
+	return nst;
 }
 
 /* ---- one stream, the separate planner (srtp_gpu_tune noplanfuse) ------ */
@@ -758,10 +808,141 @@ int rx_eligible(int op, const struct srtp *s, uint32_t pfail)
 }
 
 /*
- * One-stream unprotect batch behind such a rejection: sgpu_plan_rx, the
- * general descriptor-driven crypto launches guarded by its verdict, the
- * guarded results, one synchronisation.  hpos / hend / herr: host arrays
- * the results are copied down to as well (host-window calls), or NULL.
+ * What the two one-session receive routes (dev_rxplanned: one stream;
+ * dev_srxplanned: several) share, a call between rx1_run and its tail.
+ * Both planners take the same arrays; in and the plan out are their own
+ * structs (srx: struct sgpu_srxplan_in / _out, else sgpu_rxplan_in / _out),
+ * of which the shared code reads only the words named here.
+ */
+struct rx1 {
+	int srx;
+	const struct comp *c0;
+	const struct srtp_batch_dev *d;
+	struct ws *w;
+	const void *in;
+	size_t scr, outsz;      /* bytes: the planner's scratch, its plan out */
+	size_t o_nfail, o_skip; /* in the plan out: the crypto launches' miss
+				   counter, skip[4] (fail is its first word) */
+	/* rx1_run's */
+	struct sgpu_compact C;  /* the crypto launch */
+	uint32_t *fail_d, *skip_d;
+	const void *out;        /* the plan out, pinned */
+};
+
+/*
+ * The parse prologue, the plan, the general descriptor-driven crypto launch
+ * guarded by its verdict, the guarded results (commit), one copy back, one
+ * synchronisation.  hcopy: pos | end | err go to w->ms.h as well.  0: x->out
+ * holds the outcome, with the forged packets still to look at; -1: not
+ * settled (nothing modified); errno.
+ */
+static int rx1_run(struct rx1 *x, int hcopy)
+{
+	const struct comp *c0 = x->c0;
+	const struct srtp_batch_dev *d = x->d;
+	const int gcm = c0->mode == SGPU_MODE_GCM;
+	const size_t n = d->n;
+	const uint32_t T = gcm ? 16u : c0->tag_len;
+	const struct ws_sizes z = {
+		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
+		.vs = n * 5 + 64, .cm = 4, .pl = 64 + x->outsz, .es = n * 4};
+	struct ws_layout L;
+	struct ws *w = x->w;
+	void *stream = d->stream;
+	uint8_t *out_d;
+	int err;
+
+	err = ws_layout_reserve(w, n, &z, &L);
+	if (!err)
+		err = pool_reserve(w, &w->mscr, x->scr);
+	if (!err && hcopy)
+		err = pool_reserve(w, &w->ms, n * 12);
+	if (err)
+		return err;
+	x->out = w->pl.h;
+	out_d = w->pl.d;
+	x->fail_d = (uint32_t *)out_d;
+	x->skip_d = (uint32_t *)(out_d + x->o_skip);
+	{
+		/* one launch: parse + end copy + zeroed plan out + comp map */
+		struct sgpu_prologue pro = {
+			.end_copy = L.es, .z0 = (uint32_t *)out_d,
+			.nz0 = (uint32_t)(x->outsz / 4), .cm_out = L.cm,
+			.cm = c0->dev};
+		err = sgpu_parse_prologue(d->arena, d->arena_size, d->pos,
+					  d->end, L.hdr, NULL, (uint32_t)n, 0,
+					  &pro, stream);
+	}
+	if (!err)
+		err = x->srx ? sgpu_splan_rx(x->in, L.hdr, d->pos, L.es, d->cap,
+					     d->arena_size, L.desc, w->mscr.d,
+					     x->scr, (void *)out_d, stream)
+			     : sgpu_plan_rx(x->in, L.hdr, d->pos, L.es, d->cap,
+					    d->arena_size, L.desc, w->mscr.d,
+					    x->scr, (void *)out_d, stream);
+	/* the general kernels (EALREADY packets: MAC only): AES-CM picks the
+	 * header class from skip[], GCM has one */
+	x->C = compact_of(d, &L);
+	x->C.nfail = (uint32_t *)(out_d + x->o_nfail);
+	x->C.uniform = 1;
+	x->C.guard = gcm ? x->fail_d : x->skip_d;
+	if (!err)
+		err = sgpu_run_compact(d->arena, d->arena_size, &x->C, c0->mode,
+				       (int)c0->nr, gcm ? 0 : -1, 0, stream);
+	if (!err)
+		err = x->srx ? sgpu_splan_rx_commit((void *)out_d, L.hdr,
+						    w->mscr.d, L.es, d->pos,
+						    d->end, d->err, (uint32_t)n,
+						    T, stream)
+			     : sgpu_plan_rx_commit((void *)out_d, L.hdr,
+						   w->mscr.d, L.es, d->pos,
+						   d->end, d->err, (uint32_t)n,
+						   T, stream);
+	if (!err)
+		err = sgpu_memcpy_d2h(w->pl.h, out_d, x->outsz, stream);
+	if (!err && hcopy) {
+		err = sgpu_memcpy_d2h(w->ms.h, d->pos, n * 4, stream);
+		if (!err)
+			err = sgpu_memcpy_d2h(w->ms.h + n * 4, d->end, n * 4,
+					      stream);
+		if (!err)
+			err = sgpu_memcpy_d2h(w->ms.h + n * 8, d->err, n * 4,
+					      stream);
+	}
+	if (!err)
+		err = sgpu_stream_sync(stream);
+	if (err || !*(const uint32_t *)x->out)
+		return err;
+	if (g_env.times)
+		fprintf(stderr, "re_srtp %srx plan n=%zu: not settled "
+			"(SPF %#x)\n", x->srx ? "streams " : "", n,
+			*(const uint32_t *)x->out);
+	return -1;
+}
+
+/* a forged packet: undo on the device (the results were not written), fold
+ * on the host engine.  AES-CM: one guarded launch per header class, GCM:
+ * one */
+static int rx1_undo(struct rx1 *x)
+{
+	const struct comp *c0 = x->c0;
+	const struct srtp_batch_dev *d = x->d;
+	const int gcm = c0->mode == SGPU_MODE_GCM;
+	int q, err = 0;
+
+	x->C.undo = 1;
+	for (q = 0; q < (gcm ? 1 : 4) && !err; q++) {
+		x->C.guard = gcm ? x->fail_d : &x->skip_d[q];
+		err = sgpu_run_compact(d->arena, d->arena_size, &x->C, c0->mode,
+				       (int)c0->nr, q, 0, d->stream);
+	}
+	return undo_synced(err, d->stream);
+}
+
+/*
+ * One-stream unprotect batch behind such a rejection, planned by
+ * sgpu_plan_rx (rx1_run).  hpos / hend / herr: host arrays the results are
+ * copied down to as well (host-window calls), or NULL.
  * 0: done, the stream advanced; -1: not settled, or a forged packet
  * (undone) -- nothing modified, the caller's fallback continues; errno.
  */
@@ -772,36 +953,24 @@ int dev_rxplanned(struct srtp *s, struct srtp_batch_dev *d, uint32_t *hpos,
 	const int gcm = c0->mode == SGPU_MODE_GCM;
 	const size_t n = d->n;
 	const uint32_t T = gcm ? 16u : c0->tag_len;
-	const size_t scr = sgpu_plan_rx_scratch((uint32_t)n);
 	const struct srtp_stream *st0 = s->nstreams ? &s->streams[0] : NULL;
-	const struct ws_sizes z = {
-		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
-		.vs = n * 5 + 64, .cm = 4,
-		.pl = 64 + sizeof(struct sgpu_rxplan_out), .es = n * 4};
-	struct ws_layout L;
-	struct sgpu_compact C;
 	struct sgpu_rxplan_in in;
-	struct sgpu_rxplan_out *ro, *ro_d;
+	struct rx1 x = {
+		.c0 = c0, .d = d, .w = ws_get(), .in = &in,
+		.scr = sgpu_plan_rx_scratch((uint32_t)n),
+		.outsz = sizeof(struct sgpu_rxplan_out),
+		.o_nfail = offsetof(struct sgpu_rxplan_out, nfail),
+		.o_skip = offsetof(struct sgpu_rxplan_out, skip)};
+	const struct sgpu_rxplan_out *ro;
+	const struct ws *w = x.w;
 	struct srtp_stream *st;
-	void *stream = d->stream;
-	struct ws *w = ws_get();
-	int err, q;
+	int err;
 
 	if (!w)
 		return ENOMEM;
 	/* the rule computes in signed 64 bits (an imported window) */
 	if (st0 && (st0->replay_rtp.lix >> 62))
 		return -1;
-	err = ws_layout_reserve(w, n, &z, &L);
-	if (!err)
-		err = pool_reserve(w, &w->mscr, scr);
-	if (!err && hpos)
-		err = pool_reserve(w, &w->ms, n * 12);
-	if (err)
-		return err;
-	ro = (struct sgpu_rxplan_out *)w->pl.h;
-	ro_d = (struct sgpu_rxplan_out *)w->pl.d;
-
 	memset(&in, 0, sizeof(in));
 	in.n = (uint32_t)n;
 	in.fresh = !st0 || !st0->s_l_set;
@@ -816,68 +985,14 @@ int dev_rxplanned(struct srtp *s, struct srtp_batch_dev *d, uint32_t *hpos,
 	in.hmac = !gcm;
 	in.lookback = RX_LOOKBACK;
 	in.zeroed = 1;
-	{
-		/* one launch: parse + end copy + zeroed plan out + comp map */
-		struct sgpu_prologue pro = {
-			.end_copy = L.es, .z0 = (uint32_t *)ro_d,
-			.nz0 = (uint32_t)(sizeof(*ro) / 4), .cm_out = L.cm,
-			.cm = c0->dev};
-		err = sgpu_parse_prologue(d->arena, d->arena_size, d->pos,
-					  d->end, L.hdr, NULL, (uint32_t)n, 0,
-					  &pro, stream);
-	}
-	if (!err)
-		err = sgpu_plan_rx(&in, L.hdr, d->pos, L.es, d->cap,
-				   d->arena_size, L.desc, w->mscr.d, scr, ro_d,
-				   stream);
-	/* the general kernels (EALREADY packets: MAC only): AES-CM picks the
-	 * header class from skip[], GCM has one */
-	C = compact_of(d, &L);
-	C.nfail = &ro_d->nfail;
-	C.uniform = 1;
-	C.guard = gcm ? &ro_d->fail : ro_d->skip;
-	if (!err)
-		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
-				       (int)c0->nr, gcm ? 0 : -1, 0, stream);
-	if (!err)
-		err = sgpu_plan_rx_commit(ro_d, L.hdr, w->mscr.d, L.es, d->pos,
-					  d->end, d->err, (uint32_t)n, T, stream);
-	if (!err)
-		err = sgpu_memcpy_d2h(ro, ro_d, sizeof(*ro), stream);
-	if (!err && hpos) {
-		err = sgpu_memcpy_d2h(w->ms.h, d->pos, n * 4, stream);
-		if (!err)
-			err = sgpu_memcpy_d2h(w->ms.h + n * 4, d->end, n * 4,
-					      stream);
-		if (!err)
-			err = sgpu_memcpy_d2h(w->ms.h + n * 8, d->err, n * 4,
-					      stream);
-	}
-	if (!err)
-		err = sgpu_stream_sync(stream);
+	err = rx1_run(&x, hpos != NULL);
 	if (err)
 		return err;
-	if (ro->fail) {
-		if (g_env.times)
-			fprintf(stderr, "re_srtp rx plan n=%zu: not settled "
-				"(SPF %#x)\n", n, ro->fail);
-		return -1;
-	}
+	ro = x.out;
 	if (ro->nfail) {
-		/* a forged packet: undo on the device (the results were not
-		 * written), fold on the host engine */
 		count(&g_cnt_misses, ro->nfail);
 		count(&g_cnt_folds, 1);
-		/* AES-CM: one guarded launch per header class, GCM: one */
-		C.undo = 1;
-		for (q = 0; q < (gcm ? 1 : 4) && !err; q++) {
-			C.guard = gcm ? &ro_d->fail : &ro_d->skip[q];
-			err = sgpu_run_compact(d->arena, d->arena_size, &C,
-					       c0->mode, (int)c0->nr, q, 0, stream);
-		}
-		if (!err)
-			err = sgpu_stream_sync(stream);
-		return err ? err : -1;
+		return rx1_undo(&x);
 	}
 	if (!s->nstreams) {
 		memset(&s->streams[0], 0, sizeof(s->streams[0]));
@@ -1078,13 +1193,11 @@ int srx_eligible(int op, size_t nsess, const struct srtp_batch_dev *d,
 }
 
 /*
- * One-session unprotect batch over several SSRCs behind such a rejection:
- * the parse prologue, sgpu_splan_rx, the general descriptor-driven crypto
- * launches guarded by its verdict, the guarded results, one copy back, one
- * synchronisation; then the streams the batch opened are appended in
- * first-appearance order and every touched stream takes its record after the
- * batch.  0: done; -1: not settled, or a forged packet (undone) -- nothing
- * modified, the caller's fallback continues; errno.
+ * One-session unprotect batch over several SSRCs behind such a rejection,
+ * planned by sgpu_splan_rx (rx1_run); then the streams the batch opened are
+ * appended in first-appearance order and every touched stream takes its
+ * record after the batch.  0: done; -1: not settled, or a forged packet
+ * (undone) -- nothing modified, the caller's fallback continues; errno.
  */
 int dev_srxplanned(struct srtp *s, struct srtp_batch_dev *d)
 {
@@ -1092,112 +1205,48 @@ int dev_srxplanned(struct srtp *s, struct srtp_batch_dev *d)
 	const int gcm = c0->mode == SGPU_MODE_GCM;
 	const size_t n = d->n;
 	const uint32_t T = gcm ? 16u : c0->tag_len;
-	const size_t scr = sgpu_splan_rx_scratch((uint32_t)n);
-	const struct ws_sizes z = {
-		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
-		.vs = n * 5 + 64, .cm = 4,
-		.pl = 64 + sizeof(struct sgpu_srxplan_out), .es = n * 4};
-	struct ws_layout L;
-	struct sgpu_compact C;
 	struct sgpu_srxplan_in in;
-	struct sgpu_srxplan_out *ro, *ro_d;
-	void *stream = d->stream;
-	struct ws *w = ws_get();
-	unsigned k;
-	int err, q;
+	struct rx1 x = {
+		.srx = 1, .c0 = c0, .d = d, .w = ws_get(), .in = &in,
+		.scr = sgpu_splan_rx_scratch((uint32_t)n),
+		.outsz = sizeof(struct sgpu_srxplan_out),
+		.o_nfail = offsetof(struct sgpu_srxplan_out, tab.base.nfail),
+		.o_skip = offsetof(struct sgpu_srxplan_out, tab.base.skip)};
+	const struct sgpu_srxplan_out *ro;
+	unsigned k, nst;
+	int err;
 
-	if (!w)
+	if (!x.w)
 		return ENOMEM;
 	/* the rule computes in signed 64 bits (an imported window) */
 	for (k = 0; k < s->nstreams; k++)
 		if (s->streams[k].replay_rtp.lix >> 62)
 			return -1;
-	err = ws_layout_reserve(w, n, &z, &L);
-	if (!err)
-		err = pool_reserve(w, &w->mscr, scr);
-	if (err)
-		return err;
-	ro = (struct sgpu_srxplan_out *)w->pl.h;
-	ro_d = (struct sgpu_srxplan_out *)w->pl.d;
-
 	memset(&in, 0, sizeof(in));
 	splan_in(&in.s, s, (uint32_t)n, 0, T, 0);
 	in.s.zeroed = 1;
 	in.hmac = !gcm;
 	in.lookback = RX_LOOKBACK;
-	{
-		/* one launch: parse + end copy + zeroed plan out + comp map */
-		struct sgpu_prologue pro = {
-			.end_copy = L.es, .z0 = (uint32_t *)ro_d,
-			.nz0 = (uint32_t)(sizeof(*ro) / 4), .cm_out = L.cm,
-			.cm = c0->dev};
-		err = sgpu_parse_prologue(d->arena, d->arena_size, d->pos,
-					  d->end, L.hdr, NULL, (uint32_t)n, 0,
-					  &pro, stream);
-	}
-	if (!err)
-		err = sgpu_splan_rx(&in, L.hdr, d->pos, L.es, d->cap,
-				    d->arena_size, L.desc, w->mscr.d, scr, ro_d,
-				    stream);
-	/* the general kernels (EALREADY packets: MAC only): AES-CM picks the
-	 * header class from skip[], GCM has one */
-	C = compact_of(d, &L);
-	C.nfail = &ro_d->tab.base.nfail;
-	C.uniform = 1;
-	C.guard = gcm ? &ro_d->tab.base.fail : ro_d->tab.base.skip;
-	if (!err)
-		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
-				       (int)c0->nr, gcm ? 0 : -1, 0, stream);
-	if (!err)
-		err = sgpu_splan_rx_commit(ro_d, L.hdr, w->mscr.d, L.es, d->pos,
-					   d->end, d->err, (uint32_t)n, T, stream);
-	if (!err)
-		err = sgpu_memcpy_d2h(ro, ro_d, sizeof(*ro), stream);
-	if (!err)
-		err = sgpu_stream_sync(stream);
+	err = rx1_run(&x, 0);
 	if (err)
 		return err;
-	if (ro->tab.base.fail) {
-		if (g_env.times)
-			fprintf(stderr, "re_srtp streams rx plan n=%zu: not settled "
-				"(SPF %#x)\n", n, ro->tab.base.fail);
-		return -1;
-	}
-	if (ro->tab.base.nfail) {
-		/* a forged packet: undo on the device (the results were not
-		 * written), fold on the host engine -- which counts the misses
-		 * and the one fold, as it does without this planner */
-		/* AES-CM: one guarded launch per header class, GCM: one */
-		C.undo = 1;
-		for (q = 0; q < (gcm ? 1 : 4) && !err; q++) {
-			C.guard = gcm ? &ro_d->tab.base.fail
-				      : &ro_d->tab.base.skip[q];
-			err = sgpu_run_compact(d->arena, d->arena_size, &C,
-					       c0->mode, (int)c0->nr, q, 0, stream);
-		}
-		if (!err)
-			err = sgpu_stream_sync(stream);
-		return err ? err : -1;
-	}
-	/* new SSRCs in first-appearance order (stream_new, stream.c:45-67),
-	 * then every touched stream's record after the batch */
-	for (k = 0; k < ro->tab.nst && k < SRTP_MAX_STREAMS; k++) {
-		struct srtp_stream *x = &s->streams[k];
+	ro = x.out;
+	/* a forged packet: the host engine counts the misses and the one fold,
+	 * as it does without this planner */
+	if (ro->tab.base.nfail)
+		return rx1_undo(&x);
+	nst = streams_append(s, &ro->tab);
+	for (k = 0; k < nst; k++) {
+		struct srtp_stream *st = &s->streams[k];
 		const struct sgpu_rtp_rec *a = &ro->after[k];
-		if (k >= s->nstreams) {
-			memset(x, 0, sizeof(*x));
-			x->ssrc = ro->tab.ssrc[k];
-		}
 		if (!ro->cnt[k])
 			continue;
-		x->roc = a->roc;
-		x->s_l = (uint16_t)a->sl;
-		x->s_l_set = 1;
-		x->replay_rtp.lix = (uint64_t)a->lhi << 32 | a->llo;
-		x->replay_rtp.bitmap = (uint64_t)a->bhi << 32 | a->blo;
+		st->roc = a->roc;
+		st->s_l = (uint16_t)a->sl;
+		st->s_l_set = 1;
+		st->replay_rtp.lix = (uint64_t)a->lhi << 32 | a->llo;
+		st->replay_rtp.bitmap = (uint64_t)a->bhi << 32 | a->blo;
 	}
-	if (ro->tab.nst > s->nstreams)
-		s->nstreams = ro->tab.nst;
 	count(&g_cnt_srxplans, 1);
 	count(&g_cnt_rxlate, ro->nlate);
 	count(&g_cnt_rxdups, ro->ndup);
@@ -1247,6 +1296,42 @@ static void rplan_apply(struct srtp *s, const struct sgpu_plan_out *po,
 }
 
 /*
+ * A single-stream SRTCP call behind its synchronisation (dev_lplanned_rtcp,
+ * dev_planned_rtcp).  A rejected plan -- the crypto launch C and the results
+ * did nothing -- is -1 with its SPF_* bits in *pfail.  Else the stream
+ * advances; with a forged packet the batch is undone on the device, the
+ * stream put back and the fold left to the host engine (-1).
+ */
+static int rplanned_done(struct srtp *s, const struct srtp_batch_dev *d,
+			 const struct sgpu_plan_out *po, int prot,
+			 struct sgpu_compact C, const uint32_t *es,
+			 uint32_t *pfail)
+{
+	const unsigned ns0 = s->nstreams;
+	struct srtp_stream old;
+	int err;
+
+	if (po->fail) {
+		count(&g_cnt_rejects, 1);
+		*pfail = po->fail;
+		return -1;
+	}
+	count(&g_cnt_rplans, 1);
+	rplan_apply(s, po, prot, d->n, &old);
+	if (!po->nfail)
+		return 0;
+	count(&g_cnt_misses, po->nfail);
+	count(&g_cnt_folds, 1);
+	C.uniform = s->rtcp.mode == SGPU_MODE_GCM ? 0 : 1;
+	err = undone(undo_rtcp(d, C, &s->rtcp), d, es);
+	if (err == -1) {
+		s->streams[0] = old;
+		s->nstreams = ns0;
+	}
+	return err;
+}
+
+/*
  * Single-stream SRTCP batch planned in one launch (k_rp_plan: the parse,
  * every check of k_plan_rtcp, desc) in front of the single-key crypto
  * kernel, which it guards with out->fail and whose misses it counts in
@@ -1262,14 +1347,12 @@ static int dev_lplanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d,
 	const int gcm = c0->mode == SGPU_MODE_GCM;
 	const size_t n = d->n;
 	const uint32_t grow = 4u + c0->tag_len + (gcm ? 16u : 0u);
-	const unsigned ns0 = s->nstreams;
 	const struct ws_sizes z = {
 		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
 		.vs = n * 5 + 64, .cm = 4, .es = n * 4, .es_first = 1};
 	struct ws_layout L;
 	struct fz_layout Z;
 	struct sgpu_compact C;
-	struct srtp_stream old;
 	struct sgpu_rfused R;
 	struct sgpu_plan_out *po, *po_d;
 	void *stream = d->stream;
@@ -1326,33 +1409,11 @@ static int dev_lplanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d,
 		err = sgpu_stream_sync(stream);
 	if (err)
 		return err;
-	if (po->fail) {
-		/* the crypto launch and the results did nothing */
-		count(&g_cnt_rejects, 1);
-		if (g_env.times)
-			fprintf(stderr, "re_srtp rtcp plan n=%zu %s: rejected "
-				"(SPF %#x)\n", n, prot ? "protect" : "unprotect",
-				po->fail);
-		*pfail = po->fail;
-		return -1;
-	}
-	count(&g_cnt_rplans, 1);
-	rplan_apply(s, po, prot, n, &old);
-	if (!po->nfail)
-		return 0;
-	count(&g_cnt_misses, po->nfail);
-	count(&g_cnt_folds, 1);
-	/* a forged packet: undo on the device, fold on the host engine */
-	C.undo = 1;
-	C.uniform = gcm ? 0 : 1;
-	err = undone(sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
-				      (int)c0->nr, gcm ? 0 : 2, 0, stream),
-		     d, L.es);
-	if (err == -1) {
-		s->streams[0] = old;
-		s->nstreams = ns0;
-	}
-	return err;
+	if (po->fail && g_env.times)
+		fprintf(stderr, "re_srtp rtcp plan n=%zu %s: rejected "
+			"(SPF %#x)\n", n, prot ? "protect" : "unprotect",
+			po->fail);
+	return rplanned_done(s, d, po, prot, C, L.es, pfail);
 }
 
 /*
@@ -1375,7 +1436,6 @@ int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d,
 	const size_t n = d->n;
 	const uint32_t T = c0->tag_len;             /* 0 for GCM */
 	const uint32_t grow = 4u + T + (gcm ? 16u : 0u);
-	const unsigned ns0 = s->nstreams;
 	/* hd: the parsed headers | the E || index words */
 	const struct ws_sizes z = {
 		.hd = n * (sizeof(struct sgpu_hdr) + 12), .dsc = n * 12,
@@ -1383,10 +1443,9 @@ int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d,
 		.pl = sizeof(struct sgpu_plan_out) + 64, .es = n * 4};
 	struct ws_layout L;
 	struct sgpu_compact C;
-	struct srtp_stream old;
 	struct sgpu_rplan_in in;
 	struct sgpu_plan_out *po, *po_d;
-	uint32_t *eix_d, nfail;
+	uint32_t *eix_d;
 	void *stream = d->stream;
 	struct ws *w = ws_get();
 	int err;
@@ -1435,29 +1494,7 @@ int dev_planned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d,
 		err = sgpu_stream_sync(stream);
 	if (err)
 		return err;
-	nfail = po->nfail;
-	if (po->fail) {
-		count(&g_cnt_rejects, 1);
-		*pfail = po->fail;
-		return -1;
-	}
-	count(&g_cnt_rplans, 1);
-	rplan_apply(s, po, prot, n, &old);
-	if (!nfail)
-		return 0;
-	count(&g_cnt_misses, nfail);
-	count(&g_cnt_folds, 1);
-	/* a forged packet: undo on the device, fold on the host engine */
-	C.undo = 1;
-	C.uniform = gcm ? 0 : 1;
-	err = undone(sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
-				      (int)c0->nr, gcm ? 0 : 2, 0, stream),
-		     d, L.es);
-	if (err == -1) {
-		s->streams[0] = old;
-		s->nstreams = ns0;
-	}
-	return err;
+	return rplanned_done(s, d, po, prot, C, L.es, pfail);
 }
 
 /* ---- SRTCP, one session, several SSRCs or disturbed arrivals ------------ */
@@ -1507,7 +1544,7 @@ int dev_splanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 	uint32_t *eix_d;
 	void *stream = d->stream;
 	struct ws *w = ws_get();
-	unsigned k;
+	unsigned k, nst;
 	int err;
 
 	if (!w)
@@ -1587,22 +1624,13 @@ int dev_splanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 		 * written), fold on the host engine -- which counts the misses
 		 * and the one fold, as it does without this planner */
 		count(&g_cnt_srundos, 1);
-		C.undo = 1;
-		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
-				       (int)c0->nr, gcm ? 0 : 2, 0, stream);
-		if (!err)
-			err = sgpu_stream_sync(stream);
-		return err ? err : -1;
+		return undo_synced(undo_rtcp(d, C, c0), stream);
 	}
-	/* new SSRCs in first-appearance order (stream_new, stream.c:45-67),
-	 * then every touched stream's state after the batch */
-	for (k = 0; k < ro->tab.nst && k < SRTP_MAX_STREAMS; k++) {
+	/* every touched stream's state after the batch */
+	nst = streams_append(s, &ro->tab);
+	for (k = 0; k < nst; k++) {
 		struct srtp_stream *x = &s->streams[k];
 		const struct sgpu_rtcp_rec *a = &ro->after[k];
-		if (k >= s->nstreams) {
-			memset(x, 0, sizeof(*x));
-			x->ssrc = ro->tab.ssrc[k];
-		}
 		if (!ro->cnt[k])
 			continue;
 		if (prot) {
@@ -1613,22 +1641,174 @@ int dev_splanned_rtcp(int op, struct srtp *s, struct srtp_batch_dev *d)
 			x->replay_rtcp.bitmap = (uint64_t)a->bhi << 32 | a->blo;
 		}
 	}
-	if (ro->tab.nst > s->nstreams)
-		s->nstreams = ro->tab.nst;
 	count(&g_cnt_srplans, 1);
 	count(&g_cnt_rxlate, ro->nlate);
 	count(&g_cnt_rxdups, ro->ndup);
 	return 0;
 }
 
-/* ---- SRTCP, many sessions with up to 8 SSRCs each ---------------------- */
+/* ---- many sessions: what the bucket planners' routes share ------------- */
 
-#define BP_HEAD (512u + 4u * SGPU_BP_NBMAX)     /* w->bp: see below */
+_Static_assert(sizeof(struct sgpu_sstate) == BP_SSTATE,
+	       "bp_layout.h: sout holds one struct sgpu_sstate per session");
 
-static size_t al256(size_t x)
+/* w->pl of these routes: plan out | fold out (the scatter zeroes its fail
+ * word; only the resident in-order route folds) | the receive routes'
+ * sgpu_bprx_out */
+#define PL_FOFF ((sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63)
+
+/* bucket geometry (sgpu_bplan_geometry: -1, the buckets do not take the
+ * batch) */
+struct bgeo {
+	uint32_t bshift, nb, cap;
+};
+
+static int bgeo_get(size_t n, size_t nsess, struct bgeo *g)
 {
-	return (x + 255) & ~(size_t)255;
+	return sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &g->bshift,
+				   &g->nb, &g->cap);
 }
+
+/* a call's regions of w->bp on the device (NULL: not among its parts) */
+struct bp_ptrs {
+	void *ticket, *obins, *bcount;
+	void *tmp, *sorted, *afail, *sseg, *sout, *order, *cnt, *rs;
+};
+
+/* reserve w->bp as bp_layout.h cuts it up for the call, zero the head of a
+ * new pool (or of one a call did not finish on: w->bp_d) and hand out the
+ * call's regions; 0 / errno */
+static int bp_take(struct ws *w, size_t n, size_t nsess, const struct bgeo *g,
+		   enum bp_parts parts, void *stream, struct bp_ptrs *P)
+{
+	const struct bp_layout l = bp_layout(n, nsess, g->nb, g->cap, parts);
+	uint8_t *p;
+	int err = pool_reserve(w, &w->bp, l.total);
+
+	if (err)
+		return err;
+	p = w->bp.d;
+	if (w->bp_d != p) {
+		err = sgpu_memset(p, 0, BP_HEAD, stream);
+		if (err)
+			return err;
+		w->bp_d = p;
+	}
+#define BP_AT(f) .f = l.f ? p + l.f : NULL
+	*P = (struct bp_ptrs){
+		.ticket = p + l.ticket, .obins = p + l.obins,
+		.bcount = p + l.bcount, BP_AT(tmp), BP_AT(sorted), BP_AT(afail),
+		BP_AT(sseg), BP_AT(sout), BP_AT(order), BP_AT(cnt), BP_AT(rs)};
+#undef BP_AT
+	return 0;
+}
+
+/* a bucket route's launches or its synchronisation failed: the stream
+ * drained, so no copy still reads the host buffers, and the counters in
+ * w->bp from zero next time */
+static int bp_failed(int err, struct ws *w, void *stream)
+{
+	sgpu_stream_sync(stream);
+	w->bp_d = NULL;
+	return err;
+}
+
+/* what every RTP route fills alike of its bucket plan: the batch, the suite,
+ * the geometry, the caller's arrays, the workspace layout, the call's regions
+ * of w->bp, plan out and fold out in w->pl (pl_d); the rest zero */
+static void bplan_fill(struct sgpu_bplan *B, int prot, const struct comp *c0,
+		       const struct srtp_batch_dev *d, size_t nsess,
+		       const struct ws_layout *L, const struct bgeo *g,
+		       const struct bp_ptrs *P, uint8_t *pl_d)
+{
+	const int gcm = c0->mode == SGPU_MODE_GCM;
+	const uint32_t T = gcm ? 16u : c0->tag_len;
+
+	*B = (struct sgpu_bplan){
+		.n = (uint32_t)d->n, .nsess = (uint32_t)nsess,
+		.prot = (uint32_t)prot, .tag = T,
+		.need = prot ? (gcm ? 16u : (T > 4 ? T : 4u)) : 0u,
+		.maxlen = SGPU_CACHED_MAX(c0->mode),
+		.bshift = g->bshift, .nb = g->nb, .cap = g->cap,
+		.delta = prot ? (int32_t)T : -(int32_t)T, .gcm = (uint32_t)gcm,
+		.pos = d->pos, .end = d->end, .capv = d->cap, .sess = d->sess,
+		.posw = d->pos, .endw = d->end, .err = d->err,
+		.es = L->es, .hdr = L->hdr, .desc = L->desc, .nfail = L->nfail,
+		.ticket = P->ticket, .obins = P->obins, .bcount = P->bcount,
+		.tmp = P->tmp, .sorted = P->sorted, .afail = P->afail,
+		.sseg = P->sseg, .sout = P->sout, .order = P->order,
+		.out = (struct sgpu_plan_out *)pl_d,
+		.fo = (struct sgpu_fold_out *)(pl_d + PL_FOFF)};
+}
+
+/* the same of an SRTCP bucket plan (s0: any of the batch's sessions, for
+ * the suite) */
+static void brtcp_fill(struct sgpu_bplan_rtcp *R, int prot,
+		       const struct srtp *s0, const struct srtp_batch_dev *d,
+		       size_t nsess, const struct ws_layout *L,
+		       const struct bgeo *g, const struct bp_ptrs *P,
+		       uint8_t *pl_d)
+{
+	const struct comp *c0 = &s0->rtcp;
+	const uint32_t grow = 4u + c0->tag_len +
+			      (c0->mode == SGPU_MODE_GCM ? 16u : 0u);
+
+	*R = (struct sgpu_bplan_rtcp){
+		.nsess = (uint32_t)nsess,
+		.bshift = g->bshift, .nb = g->nb, .cap = g->cap,
+		.delta = prot ? (int32_t)grow : -(int32_t)grow,
+		.pos = d->pos, .end = d->end, .capv = d->cap, .sess = d->sess,
+		.endw = d->end, .err = d->err,
+		.es = L->es, .hdr = L->hdr, .desc = L->desc, .nfail = L->nfail,
+		.bcount = P->bcount, .tmp = P->tmp, .afail = P->afail,
+		.out = (struct sgpu_plan_out *)pl_d};
+	/* the suite's part of the plan input; the streams come in the tables */
+	rplan_in(&R->in, s0, (uint32_t)d->n, prot);
+	R->in.ssrc_any = 0;
+	R->in.ssrc = R->in.rtcp_index = 0;
+	R->in.lix = R->in.bitmap = 0;
+}
+
+/*
+ * The table routes plan against the host's stream tables: one upload in
+ * w->ms (cm | toff | recs, the gathered part of it), one download of the
+ * touched tables from w->mscr (sinfo | sout).  A receive route works on the
+ * upload of the in-order route before it.
+ */
+struct tab_layout {
+	size_t o_toff, o_recs;  /* in w->ms (cm: 0) */
+	size_t up_max;          /* ... its bytes with every table full */
+	size_t o_sout;          /* in w->mscr (sinfo: 0) */
+	size_t down;            /* ... its bytes */
+};
+
+/* rec: bytes of a stream record (struct sgpu_rtp_rec / sgpu_rtcp_rec) */
+static struct tab_layout tab_layout(size_t nsess, size_t rec)
+{
+	struct tab_layout t;
+	t.o_toff = bp_al256(nsess * 4);
+	t.o_recs = t.o_toff + bp_al256((nsess + 1) * 4);
+	t.up_max = t.o_recs + nsess * SRTP_MAX_STREAMS * rec;
+	t.o_sout = bp_al256(nsess * 4);
+	t.down = t.o_sout + nsess * SRTP_MAX_STREAMS * rec;
+	return t;
+}
+
+static int tab_reserve(struct ws *w, const struct tab_layout *t)
+{
+	int err = pool_reserve(w, &w->ms, t->up_max);
+	if (!err)
+		err = pool_reserve(w, &w->mscr, t->down);
+	return err;
+}
+
+/* the upload must be the in-order route's: never a new pool */
+static int tab_uploaded(const struct ws *w, const struct tab_layout *t)
+{
+	return w->ms.cap >= t->up_max && w->mscr.cap >= t->down;
+}
+
+/* ---- SRTCP, many sessions with up to 8 SSRCs each ---------------------- */
 
 /*
  * An SRTCP protect / unprotect batch over many sessions, every array in
@@ -1643,9 +1823,7 @@ static size_t al256(size_t x)
  * counted), a rejected plan, or a forged packet (undone) -- nothing
  * modified, the caller's fallback continues; errno.
  *
- * w->ms: cm | toff | recs (up); w->mscr: sinfo | sout (down); w->bp:
- * BP_HEAD as dev_bplanned_issue lays it out (the bucket counters at 512,
- * zero between calls) | bucket entries | fail words.
+ * w->ms, w->mscr: struct tab_layout; w->bp: BP_TABLE (bp_layout.h).
  */
 int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 		      struct srtp_batch_dev *d, uint32_t *pfail)
@@ -1654,23 +1832,19 @@ int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 	const struct comp *c0 = &sessv[0]->rtcp;
 	const int gcm = c0->mode == SGPU_MODE_GCM;
 	const size_t n = d->n;
-	const uint32_t grow = 4u + c0->tag_len + (gcm ? 16u : 0u);
-	const size_t na = (n + SGPU_BP_BLOCK * SGPU_BP_PPT - 1) /
-			  (SGPU_BP_BLOCK * SGPU_BP_PPT);
-	const size_t o_toff = al256(nsess * 4);
-	const size_t o_recs = o_toff + al256((nsess + 1) * 4);
-	const size_t o_sout = al256(nsess * 4);
-	const size_t down = o_sout +
-			    nsess * SRTP_MAX_STREAMS * sizeof(struct sgpu_rtcp_rec);
+	const struct tab_layout tab =
+		tab_layout(nsess, sizeof(struct sgpu_rtcp_rec));
 	const struct ws_sizes z = {
 		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
 		.vs = n * 5 + 64, .cm = 4,
 		.pl = sizeof(struct sgpu_plan_out) + 64, .es = n * 4};
 	struct ws_layout L;
+	struct bgeo g;
+	struct bp_ptrs P;
 	struct sgpu_bplan_rtcp R;
 	struct sgpu_compact C;
 	struct sgpu_plan_out *po, *po_d;
-	uint32_t *toff_h, bshift, nb, cap;
+	uint32_t *toff_h;
 	size_t up;
 	void *stream = d->stream;
 	struct ws *w;
@@ -1679,68 +1853,33 @@ int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 	int err;
 
 	*pfail = 0;
-	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
+	if (bgeo_get(n, nsess, &g))
 		return -1;
 	w = ws_get();
 	if (!w)
 		return ENOMEM;
 	err = ws_layout_reserve(w, n, &z, &L);
 	if (!err)
-		err = pool_reserve(w, &w->ms, o_recs + nsess * SRTP_MAX_STREAMS *
-				   sizeof(struct sgpu_rtcp_rec));
+		err = tab_reserve(w, &tab);
 	if (!err)
-		err = pool_reserve(w, &w->mscr, down);
-	if (!err)
-		err = pool_reserve(w, &w->bp, BP_HEAD +
-				   al256((size_t)nb * cap * 16) + al256(na * 4));
+		err = bp_take(w, n, nsess, &g, BP_TABLE, stream, &P);
 	if (err)
 		return err;
-	toff_h = (uint32_t *)(w->ms.h + o_toff);
+	toff_h = (uint32_t *)(w->ms.h + tab.o_toff);
 	t[0] = times ? now_ms() : 0;
 	if (mrplan_gather(sessv, nsess, prot, toff_h,
-			  (struct sgpu_rtcp_rec *)(w->ms.h + o_recs),
+			  (struct sgpu_rtcp_rec *)(w->ms.h + tab.o_recs),
 			  (uint32_t *)w->ms.h))
 		return -1;
-	up = o_recs + (size_t)toff_h[nsess] * sizeof(struct sgpu_rtcp_rec);
+	up = tab.o_recs + (size_t)toff_h[nsess] * sizeof(struct sgpu_rtcp_rec);
 	t[1] = times ? now_ms() : 0;
-	if (w->bp_d != w->bp.d) {
-		/* a new pool (or a call that did not finish): counters from
-		 * zero */
-		err = sgpu_memset(w->bp.d, 0, BP_HEAD, stream);
-		if (err)
-			return err;
-		w->bp_d = w->bp.d;
-	}
 	po = (struct sgpu_plan_out *)w->pl.h;
 	po_d = (struct sgpu_plan_out *)w->pl.d;
-	memset(&R, 0, sizeof(R));
-	rplan_in(&R.in, sessv[0], (uint32_t)n, prot);
-	R.in.ssrc_any = 0;
-	R.in.ssrc = R.in.rtcp_index = 0;
-	R.in.lix = R.in.bitmap = 0;
-	R.nsess = (uint32_t)nsess;
-	R.bshift = bshift;
-	R.nb = nb;
-	R.cap = cap;
-	R.delta = prot ? (int32_t)grow : -(int32_t)grow;
-	R.pos = d->pos;
-	R.end = d->end;
-	R.capv = d->cap;
-	R.sess = d->sess;
-	R.endw = d->end;
-	R.err = d->err;
-	R.es = L.es;
-	R.hdr = L.hdr;
-	R.desc = L.desc;
-	R.bcount = (uint32_t *)(w->bp.d + 512);
-	R.tmp = (void *)(w->bp.d + BP_HEAD);
-	R.afail = (uint32_t *)(w->bp.d + BP_HEAD + al256((size_t)nb * cap * 16));
-	R.toff = (const uint32_t *)(w->ms.d + o_toff);
-	R.recs = (const struct sgpu_rtcp_rec *)(w->ms.d + o_recs);
+	brtcp_fill(&R, prot, sessv[0], d, nsess, &L, &g, &P, w->pl.d);
+	R.toff = (const uint32_t *)(w->ms.d + tab.o_toff);
+	R.recs = (const struct sgpu_rtcp_rec *)(w->ms.d + tab.o_recs);
 	R.sinfo = (uint32_t *)w->mscr.d;
-	R.sout = (struct sgpu_rtcp_rec *)(w->mscr.d + o_sout);
-	R.out = po_d;
-	R.nfail = L.nfail;
+	R.sout = (struct sgpu_rtcp_rec *)(w->mscr.d + tab.o_sout);
 	R.outbytes = (uint32_t)offsetof(struct sgpu_plan_out, tail_ix);
 	R.outh = g_env.nopost ? NULL : (uint32_t *)po;
 	srv_stop(w);
@@ -1764,16 +1903,13 @@ int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 	if (!err && g_env.nopost)
 		err = sgpu_memcpy_d2h(po, po_d, R.outbytes, stream);
 	if (!err)
-		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, down, stream);
+		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, tab.down, stream);
 	t[2] = times ? now_ms() : 0;
 	if (!err)
 		err = sgpu_stream_sync(stream);
 	t[3] = times ? now_ms() : 0;
-	if (err) {
-		sgpu_stream_sync(stream);       /* no copy still reads ms.h */
-		w->bp_d = NULL;
-		return err;
-	}
+	if (err)
+		return bp_failed(err, w, stream);
 	if (po->fail) {
 		/* the crypto launch and the results did nothing */
 		count(&g_cnt_rejects, 1);
@@ -1790,15 +1926,10 @@ int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 		 * the host's tables are as they were), fold on the host engine */
 		count(&g_cnt_misses, po->nfail);
 		count(&g_cnt_folds, 1);
-		C.undo = 1;
-		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
-				       (int)c0->nr, gcm ? 0 : 2, 0, stream);
-		if (!err)
-			err = sgpu_stream_sync(stream);
-		return err ? err : -1;
+		return undo_synced(undo_rtcp(d, C, c0), stream);
 	}
 	mrplan_apply(sessv, nsess, prot, (const uint32_t *)w->mscr.h,
-		     (const struct sgpu_rtcp_rec *)(w->mscr.h + o_sout));
+		     (const struct sgpu_rtcp_rec *)(w->mscr.h + tab.o_sout));
 	if (times)
 		fprintf(stderr, "re_srtp mrtcp plan n=%zu nsess=%zu %s: gather "
 			"%.3f submit %.3f wait %.3f apply %.3f ms\n", n, nsess,
@@ -1831,101 +1962,58 @@ int mrrx_eligible(int op, const struct srtp *s, uint32_t pfail)
  * 0: done; -1: not settled, or a forged packet (undone) -- nothing modified,
  * the caller's fallback continues; errno.
  *
- * w->ms, w->mscr as in dev_mplanned_rtcp; w->bp: BP_HEAD | bucket entries |
- * fail words | per-bucket counts | verdict bytes; w->pl: plan out |
- * sgpu_bprx_out.
+ * w->ms, w->mscr: struct tab_layout, as dev_mplanned_rtcp left them; w->bp:
+ * BP_TABLE_RX (bp_layout.h); w->pl: plan out | sgpu_bprx_out.
  */
 int dev_mrrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 {
 	const struct comp *c0 = &sessv[0]->rtcp;
 	const size_t n = d->n;
-	const uint32_t grow = 4u + c0->tag_len;
-	const size_t na = (n + SGPU_BP_BLOCK * SGPU_BP_PPT - 1) /
-			  (SGPU_BP_BLOCK * SGPU_BP_PPT);
-	const size_t o_toff = al256(nsess * 4);
-	const size_t o_recs = o_toff + al256((nsess + 1) * 4);
-	const size_t o_sout = al256(nsess * 4);
-	const size_t down = o_sout +
-			    nsess * SRTP_MAX_STREAMS * sizeof(struct sgpu_rtcp_rec);
-	const size_t roff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
+	const struct tab_layout tab =
+		tab_layout(nsess, sizeof(struct sgpu_rtcp_rec));
 	const struct ws_sizes z = {
 		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
-		.vs = n * 5 + 64, .cm = 4, .pl = roff + 64, .es = n * 4};
+		.vs = n * 5 + 64, .cm = 4, .pl = PL_FOFF + 64, .es = n * 4};
 	struct ws_layout L;
+	struct bgeo g;
+	struct bp_ptrs P;
 	struct sgpu_bplan_rtcp_rx X;
 	struct sgpu_bplan_rtcp *R = &X.r;
 	struct sgpu_compact C;
 	struct sgpu_plan_out *po, *po_d;
 	const struct sgpu_bprx_out *ro;
-	uint32_t bshift, nb, cap;
-	size_t o_afail, o_cnt, o_rs;
 	void *stream = d->stream;
 	struct ws *w;
 	int err;
 
 	if (c0->mode == SGPU_MODE_GCM || !c0->has_hmac)
 		return -1;
-	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
+	if (bgeo_get(n, nsess, &g))
 		return -1;
 	w = ws_get();
 	if (!w)
 		return ENOMEM;
-	/* the upload must be the one dev_mplanned_rtcp made: never a new pool */
-	if (w->ms.cap < o_recs + nsess * SRTP_MAX_STREAMS *
-			 sizeof(struct sgpu_rtcp_rec) || w->mscr.cap < down)
+	if (!tab_uploaded(w, &tab))
 		return -1;
-	o_afail = BP_HEAD + al256((size_t)nb * cap * 16);
-	o_cnt = o_afail + al256(na * 4);
-	o_rs = o_cnt + al256((size_t)nb * 8);
 	err = ws_layout_reserve(w, n, &z, &L);
 	if (!err)
-		err = pool_reserve(w, &w->bp, o_rs + al256(n));
+		err = bp_take(w, n, nsess, &g, BP_TABLE_RX, stream, &P);
 	if (err)
 		return err;
-	if (w->bp_d != w->bp.d) {
-		/* a new pool (or a call that did not finish): counters from
-		 * zero */
-		err = sgpu_memset(w->bp.d, 0, BP_HEAD, stream);
-		if (err)
-			return err;
-		w->bp_d = w->bp.d;
-	}
 	po = (struct sgpu_plan_out *)w->pl.h;
 	po_d = (struct sgpu_plan_out *)w->pl.d;
-	ro = (const struct sgpu_bprx_out *)(w->pl.h + roff);
+	ro = (const struct sgpu_bprx_out *)(w->pl.h + PL_FOFF);
 	memset(&X, 0, sizeof(X));
-	rplan_in(&R->in, sessv[0], (uint32_t)n, 0);
-	R->in.ssrc_any = 0;
-	R->in.ssrc = R->in.rtcp_index = 0;
-	R->in.lix = R->in.bitmap = 0;
-	R->nsess = (uint32_t)nsess;
-	R->bshift = bshift;
-	R->nb = nb;
-	R->cap = cap;
-	R->delta = -(int32_t)grow;
-	R->pos = d->pos;
-	R->end = d->end;
-	R->capv = d->cap;
-	R->sess = d->sess;
-	R->endw = d->end;
-	R->err = d->err;
-	R->es = L.es;
-	R->hdr = L.hdr;
-	R->desc = L.desc;
-	R->bcount = (uint32_t *)(w->bp.d + 512);
-	R->tmp = (void *)(w->bp.d + BP_HEAD);
-	R->afail = (uint32_t *)(w->bp.d + o_afail);
-	R->toff = (const uint32_t *)(w->ms.d + o_toff);
-	R->recs = (const struct sgpu_rtcp_rec *)(w->ms.d + o_recs);
+	brtcp_fill(R, 0, sessv[0], d, nsess, &L, &g, &P, w->pl.d);
+	R->toff = (const uint32_t *)(w->ms.d + tab.o_toff);
+	R->recs = (const struct sgpu_rtcp_rec *)(w->ms.d + tab.o_recs);
 	R->sinfo = (uint32_t *)w->mscr.d;
-	R->sout = (struct sgpu_rtcp_rec *)(w->mscr.d + o_sout);
-	R->out = po_d;
-	R->nfail = L.nfail;
-	R->outbytes = (uint32_t)(roff + sizeof(struct sgpu_bprx_out));
+	R->sout = (struct sgpu_rtcp_rec *)(w->mscr.d + tab.o_sout);
+	R->outbytes = (uint32_t)(PL_FOFF + sizeof(struct sgpu_bprx_out));
 	R->outh = g_env.nopost ? NULL : (uint32_t *)po;
-	X.cnt = (uint32_t *)(w->bp.d + o_cnt);
-	X.rs = w->bp.d + o_rs;
-	X.ro = (struct sgpu_bprx_out *)(w->pl.d + roff);
+	X.cnt = P.cnt;
+	X.rs = P.rs;
+	X.ro = (struct sgpu_bprx_out *)(w->pl.d + PL_FOFF);
 	X.lookback = RX_LOOKBACK;
 	srv_stop(w);
 	{
@@ -1952,14 +2040,11 @@ int dev_mrrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 	if (!err && g_env.nopost)
 		err = sgpu_memcpy_d2h(po, po_d, R->outbytes, stream);
 	if (!err)
-		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, down, stream);
+		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, tab.down, stream);
 	if (!err)
 		err = sgpu_stream_sync(stream);
-	if (err) {
-		sgpu_stream_sync(stream);
-		w->bp_d = NULL;
-		return err;
-	}
+	if (err)
+		return bp_failed(err, w, stream);
 	if (po->fail) {
 		/* the crypto launch and the results did nothing (the rejection
 		 * was counted: dev_mplanned_rtcp's) */
@@ -1974,17 +2059,12 @@ int dev_mrrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 		 * the host's tables are as they were), fold on the host engine */
 		count(&g_cnt_misses, po->nfail);
 		count(&g_cnt_folds, 1);
-		C.undo = 1;
-		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
-				       (int)c0->nr, 2, 0, stream);
-		if (!err)
-			err = sgpu_stream_sync(stream);
-		return err ? err : -1;
+		return undo_synced(undo_rtcp(d, C, c0), stream);
 	}
 	count(&g_cnt_rxlate, ro->nlate);
 	count(&g_cnt_rxdups, ro->ndup);
 	mrplan_apply(sessv, nsess, 0, (const uint32_t *)w->mscr.h,
-		     (const struct sgpu_rtcp_rec *)(w->mscr.h + o_sout));
+		     (const struct sgpu_rtcp_rec *)(w->mscr.h + tab.o_sout));
 	return 0;
 }
 
@@ -2025,12 +2105,9 @@ static int mfold(struct dcall *k, int phase, const uint32_t *nfail,
  * same plan, verdict fold and resident states as below, in three launches
  * around the crypto instead of ~17 plus the fold's five.
  *
- * w->bp: ticket words | bin counters | bucket counters (BP_HEAD, zero
- * between calls) | bucket entries | sorted | fail words | sseg | sout |
- * launch order
+ * w->bp: BP_RESIDENT (bp_layout.h); w->pl: plan out | fold out
  */
-static int dev_bplanned_issue(struct dcall *k, uint32_t bshift, uint32_t nb,
-			      uint32_t cap)
+static int dev_bplanned_issue(struct dcall *k, const struct bgeo *g)
 {
 	const int prot = k->op == OP_RTP_ENC;
 	struct srtp **sessv = k->sessv;
@@ -2040,91 +2117,35 @@ static int dev_bplanned_issue(struct dcall *k, uint32_t bshift, uint32_t nb,
 	const struct comp *c0 = &sessv[0]->rtp;
 	const size_t n = d->n;
 	const int gcm = c0->mode == SGPU_MODE_GCM;
-	const uint32_t T = gcm ? 16u : c0->tag_len;
-	const size_t na = (n + SGPU_BP_BLOCK * SGPU_BP_PPT - 1) /
-			  (SGPU_BP_BLOCK * SGPU_BP_PPT);
 	struct sgpu_bplan *B = &k->bp;
+	struct bp_ptrs P;
 	struct sgpu_sstate *up_h, *up_d;
-	uint8_t *need_h, *need_d, *p;
+	uint8_t *need_h, *need_d;
 	uint32_t *cm_h;
 	void *stream = d->stream;
 	const int times = g_env.times;
-	/* pl: plan out | fold out */
-	const size_t foff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
 	const struct ws_sizes z = {
 		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
-		.vs = n * 9 + 72, .cm = nsess * 4, .pl = foff + 64,
+		.vs = n * 9 + 72, .cm = nsess * 4, .pl = PL_FOFF + 64,
 		.es = n * 4};
 	struct ws_layout L;
 	int err;
 
-	k->foff = foff;
+	k->foff = PL_FOFF;
 	err = ws_layout_reserve(w, n, &z, &L);
 	if (!err)   /* uploads | need */
 		err = pool_reserve(w, &w->ms,
 				   nsess * (sizeof(struct sgpu_sstate) + 1));
 	if (!err)
-		err = pool_reserve(w, &w->bp, BP_HEAD +
-				   sgpu_bplan_scratch((uint32_t)n,
-						      (uint32_t)nsess, nb, cap) +
-				   n * 4 + 256);
+		err = bp_take(w, n, nsess, g, BP_RESIDENT, stream, &P);
 	if (err)
 		return err;
-	if (w->bp_d != w->bp.d) {
-		/* a new pool (or a call that did not finish): counters and
-		 * tickets from zero */
-		err = sgpu_memset(w->bp.d, 0, BP_HEAD, stream);
-		if (err)
-			return err;
-		w->bp_d = w->bp.d;
-	}
-	memset(B, 0, sizeof(*B));
-	B->n = (uint32_t)n;
-	B->nsess = (uint32_t)nsess;
-	B->prot = (uint32_t)prot;
-	B->tag = T;
-	B->need = prot ? (gcm ? 16u : (T > 4 ? T : 4u)) : 0u;
-	B->maxlen = SGPU_CACHED_MAX(c0->mode);
-	B->bshift = bshift;
-	B->nb = nb;
-	B->cap = cap;
-	B->delta = prot ? (int32_t)T : -(int32_t)T;
-	B->gcm = (uint32_t)gcm;
+	bplan_fill(B, prot, c0, d, nsess, &L, g, &P, w->pl.d);
 	k->devfold = !prot && !g_env.nodevfold;
 	B->nofold = (uint32_t)!k->devfold;
-	B->pos = d->pos;
-	B->end = d->end;
-	B->capv = d->cap;
-	B->sess = d->sess;
-	B->posw = d->pos;
-	B->endw = d->end;
-	B->err = d->err;
-	B->es = L.es;
-	B->hdr = L.hdr;
-	B->desc = L.desc;
-	p = w->bp.d;
-	B->ticket = (uint32_t *)p;
-	B->obins = (uint32_t *)(p + 64);
-	B->bcount = (uint32_t *)(p + 512);
-	p += BP_HEAD;
-#define BP_TAKE(ptr, bytes)                                                  \
-	do {                                                                 \
-		(ptr) = (void *)p;                                           \
-		p += ((size_t)(bytes) + 255) & ~(size_t)255;                 \
-	} while (0)
-	BP_TAKE(B->tmp, (size_t)nb * cap * 16);
-	BP_TAKE(B->sorted, (size_t)nb * cap * 4);
-	BP_TAKE(B->afail, na * 4);
-	BP_TAKE(B->sseg, nsess * 4);
-	BP_TAKE(B->sout, nsess * sizeof(struct sgpu_sstate));
-	BP_TAKE(B->order, n * 4);
-#undef BP_TAKE
 	B->sst = sgpu_sst_table();
-	B->out = (struct sgpu_plan_out *)w->pl.d;
-	B->fo = (struct sgpu_fold_out *)(w->pl.d + k->foff);
 	B->pred = k->pred;
 	B->gate = k->gate;
-	B->nfail = L.nfail;
 	B->verdict = L.verdict;
 	B->flist = !prot && !gcm && k->devfold ? L.flist : NULL;
 	/* parse, checks, bucket slots: no session state needed, so it runs
@@ -2212,12 +2233,11 @@ static int dev_bplanned_issue(struct dcall *k, uint32_t bshift, uint32_t nb,
 int dev_mplanned_issue(struct dcall *k)
 {
 	{
-		uint32_t bsh, nb, cap;
+		struct bgeo g;
 		if (!k->radix && !g_env.mpradix && !g_env.nobucket &&
-		    !sgpu_bplan_geometry((uint32_t)k->d.n, (uint32_t)k->nsess,
-					 &bsh, &nb, &cap)) {
+		    !bgeo_get(k->d.n, k->nsess, &g)) {
 			k->bucket = 1;
-			return dev_bplanned_issue(k, bsh, nb, cap);
+			return dev_bplanned_issue(k, &g);
 		}
 		k->bucket = 0;
 	}
@@ -2236,7 +2256,7 @@ int dev_mplanned_issue(struct dcall *k)
 	struct sgpu_sstate *up_h, *up_d, *sin_d, *sout_d;
 	struct sgpu_mplan_in in;
 	/* pl: plan out | fold out | fold scratch (multi-session fold) */
-	const size_t foff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
+	const size_t foff = PL_FOFF;
 	const struct ws_sizes z = {
 		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 12,
 		.vs = n * 9 + 72, .cm = nsess * 4,
@@ -2520,36 +2540,34 @@ int mrx_eligible(int op, size_t nsess, uint32_t pfail)
  * forged packet (undone) -- nothing modified, the caller's fallback
  * continues; errno.
  *
- * w->bp as dev_bplanned_issue lays it out, with the per-bucket counts and
- * the verdict bytes in place of the launch order; w->pl: plan out | fold out
- * (unused) | sgpu_bprx_out.
+ * w->bp: BP_RESIDENT_RX (bp_layout.h); w->pl: plan out | fold out (unused) |
+ * sgpu_bprx_out.
  */
 int dev_mrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 {
 	const struct comp *c0 = &sessv[0]->rtp;
 	const size_t n = d->n;
 	const int gcm = c0->mode == SGPU_MODE_GCM;
-	const uint32_t T = gcm ? 16u : c0->tag_len;
-	const size_t na = (n + SGPU_BP_BLOCK * SGPU_BP_PPT - 1) /
-			  (SGPU_BP_BLOCK * SGPU_BP_PPT);
-	const size_t roff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
 	const struct ws_sizes z = {
 		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
-		.vs = n * 5 + 64, .cm = nsess * 4, .pl = roff + 128, .es = n * 4};
+		.vs = n * 5 + 64, .cm = nsess * 4, .pl = PL_FOFF + 128,
+		.es = n * 4};
 	struct ws_layout L;
+	struct bgeo g;
+	struct bp_ptrs P;
 	struct sgpu_bplan_rx R;
 	struct sgpu_bplan *B = &R.b;
 	struct sgpu_compact C;
 	struct sgpu_plan_out *po, *po_d;
 	const struct sgpu_bprx_out *ro;
 	struct sgpu_sstate *up_h, *up_d;
-	uint8_t *need_h, *need_d, *p;
-	uint32_t *cm_h, bshift, nb, cap, nup = 0;
+	uint8_t *need_h, *need_d;
+	uint32_t *cm_h, nup = 0;
 	void *stream = d->stream;
 	struct ws *w;
 	int err;
 
-	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
+	if (bgeo_get(n, nsess, &g))
 		return -1;
 	w = ws_get();
 	if (!w)
@@ -2559,68 +2577,19 @@ int dev_mrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 		err = pool_reserve(w, &w->ms,
 				   nsess * (sizeof(struct sgpu_sstate) + 1));
 	if (!err)
-		err = pool_reserve(w, &w->bp, BP_HEAD +
-				   sgpu_bplan_scratch((uint32_t)n, (uint32_t)nsess,
-						      nb, cap) +
-				   (size_t)nb * 8 + n + 512);
+		err = bp_take(w, n, nsess, &g, BP_RESIDENT_RX, stream, &P);
 	if (err)
 		return err;
-	if (w->bp_d != w->bp.d) {
-		/* a new pool (or a call that did not finish): counters from
-		 * zero */
-		err = sgpu_memset(w->bp.d, 0, BP_HEAD, stream);
-		if (err)
-			return err;
-		w->bp_d = w->bp.d;
-	}
 	po = (struct sgpu_plan_out *)w->pl.h;
 	po_d = (struct sgpu_plan_out *)w->pl.d;
-	ro = (const struct sgpu_bprx_out *)(w->pl.h + roff + 64);
+	ro = (const struct sgpu_bprx_out *)(w->pl.h + PL_FOFF + 64);
 	memset(&R, 0, sizeof(R));
-	B->n = (uint32_t)n;
-	B->nsess = (uint32_t)nsess;
-	B->tag = T;
-	B->maxlen = SGPU_CACHED_MAX(c0->mode);
-	B->bshift = bshift;
-	B->nb = nb;
-	B->cap = cap;
-	B->delta = -(int32_t)T;
-	B->gcm = (uint32_t)gcm;
-	B->pos = d->pos;
-	B->end = d->end;
-	B->capv = d->cap;
-	B->sess = d->sess;
-	B->posw = d->pos;
-	B->endw = d->end;
-	B->err = d->err;
-	B->es = L.es;
-	B->hdr = L.hdr;
-	B->desc = L.desc;
-	p = w->bp.d;
-	B->ticket = (uint32_t *)p;
-	B->obins = (uint32_t *)(p + 64);
-	B->bcount = (uint32_t *)(p + 512);
-	p += BP_HEAD;
-#define BP_TAKE(ptr, bytes)                                                  \
-	do {                                                                 \
-		(ptr) = (void *)p;                                           \
-		p += ((size_t)(bytes) + 255) & ~(size_t)255;                 \
-	} while (0)
-	BP_TAKE(B->tmp, (size_t)nb * cap * 16);
-	BP_TAKE(B->sorted, (size_t)nb * cap * 4);
-	BP_TAKE(B->afail, na * 4);
-	BP_TAKE(B->sseg, nsess * 4);
-	BP_TAKE(B->sout, nsess * sizeof(struct sgpu_sstate));
-	BP_TAKE(R.cnt, (size_t)nb * 8);
-	BP_TAKE(R.rs, n);
-#undef BP_TAKE
+	bplan_fill(B, 0, c0, d, nsess, &L, &g, &P, w->pl.d);
 	B->sst = sgpu_sst_table();
-	B->out = po_d;
-	/* (the scatter zeroes fo->fail; nothing else uses the fold out) */
-	B->fo = (struct sgpu_fold_out *)(w->pl.d + roff);
-	R.ro = (struct sgpu_bprx_out *)(w->pl.d + roff + 64);
-	B->nfail = L.nfail;
 	B->verdict = L.verdict;
+	R.cnt = P.cnt;
+	R.rs = P.rs;
+	R.ro = (struct sgpu_bprx_out *)(w->pl.d + PL_FOFF + 64);
 	R.lookback = RX_LOOKBACK;
 	R.hmac = !gcm;
 	err = sgpu_bplan_scatter(d->arena, d->arena_size, B, stream);
@@ -2661,7 +2630,7 @@ int dev_mrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 	if (!err)
 		err = sgpu_run_compact(d->arena, d->arena_size, &C, c0->mode,
 				       (int)c0->nr, gcm ? 0 : -1, 0, stream);
-	B->outbytes = (uint32_t)(roff + 64 + sizeof(struct sgpu_bprx_out));
+	B->outbytes = (uint32_t)(PL_FOFF + 64 + sizeof(struct sgpu_bprx_out));
 	B->outh = g_env.nopost ? NULL : (uint32_t *)w->pl.h;
 	if (!err)
 		err = sgpu_bplan_rx_finish(&R, stream);
@@ -2669,11 +2638,8 @@ int dev_mrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 		err = sgpu_memcpy_d2h(w->pl.h, w->pl.d, B->outbytes, stream);
 	if (!err)
 		err = sgpu_stream_sync(stream);
-	if (err) {
-		sgpu_stream_sync(stream);       /* no copy still reads cm_h */
-		w->bp_d = NULL;
-		return err;
-	}
+	if (err)
+		return bp_failed(err, w, stream);
 	if (po->fail) {
 		if (g_env.times)
 			fprintf(stderr, "re_srtp mrx plan n=%zu nsess=%zu: not "
@@ -2686,10 +2652,8 @@ int dev_mrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 		count(&g_cnt_misses, po->nfail);
 		count(&g_cnt_folds, 1);
 		C.undo = 1;
-		err = run_classes(d->arena, d->arena_size, C, c0, po_d, 0, stream);
-		if (!err)
-			err = sgpu_stream_sync(stream);
-		return err ? err : -1;
+		return undo_synced(run_classes(d->arena, d->arena_size, C, c0,
+					       po_d, 0, stream), stream);
 	}
 	count(&g_cnt_mrxplans, 1);
 	count(&g_cnt_rxlate, ro->nlate);
@@ -2730,10 +2694,8 @@ int ms_eligible(int op, size_t nsess, uint32_t pfail)
  * counted), a rejected plan, or a forged packet (undone) -- nothing
  * modified, the caller's fallback continues; errno.
  *
- * w->ms: cm | toff | recs (up); w->mscr: sinfo | sout (down); w->bp: as
- * dev_bplanned_issue lays it out as far as the scatter uses it (BP_HEAD, zero
- * between calls | bucket entries | fail words); w->pl: plan out | fold out
- * (the scatter zeroes its fail word; not used).
+ * w->ms, w->mscr: struct tab_layout; w->bp: BP_TABLE (bp_layout.h), what the
+ * scatter uses; w->pl: plan out | fold out (not used).
  */
 int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
 		  struct srtp_batch_dev *d, int counted, uint32_t *pfail)
@@ -2741,25 +2703,20 @@ int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
 	const int prot = op == OP_RTP_ENC;
 	const struct comp *c0 = &sessv[0]->rtp;
 	const int gcm = c0->mode == SGPU_MODE_GCM;
-	const uint32_t T = gcm ? 16u : c0->tag_len;
 	const size_t n = d->n;
-	const size_t na = (n + SGPU_BP_BLOCK * SGPU_BP_PPT - 1) /
-			  (SGPU_BP_BLOCK * SGPU_BP_PPT);
-	const size_t o_toff = al256(nsess * 4);
-	const size_t o_recs = o_toff + al256((nsess + 1) * 4);
-	const size_t o_sout = al256(nsess * 4);
-	const size_t down = o_sout +
-			    nsess * SRTP_MAX_STREAMS * sizeof(struct sgpu_rtp_rec);
-	const size_t foff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
+	const struct tab_layout tab =
+		tab_layout(nsess, sizeof(struct sgpu_rtp_rec));
 	const struct ws_sizes z = {
 		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
-		.vs = n * 5 + 64, .cm = 4, .pl = foff + 64, .es = n * 4};
+		.vs = n * 5 + 64, .cm = 4, .pl = PL_FOFF + 64, .es = n * 4};
 	struct ws_layout L;
+	struct bgeo g;
+	struct bp_ptrs P;
 	struct sgpu_bplan_rtps R;
 	struct sgpu_bplan *B = &R.b;
 	struct sgpu_compact C;
 	struct sgpu_plan_out *po, *po_d;
-	uint32_t *toff_h, bshift, nb, cap;
+	uint32_t *toff_h;
 	size_t up;
 	void *stream = d->stream;
 	struct ws *w;
@@ -2768,77 +2725,37 @@ int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
 	int err;
 
 	*pfail = 0;
-	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
+	if (bgeo_get(n, nsess, &g))
 		return -1;
 	w = ws_get();
 	if (!w)
 		return ENOMEM;
 	err = ws_layout_reserve(w, n, &z, &L);
 	if (!err)
-		err = pool_reserve(w, &w->ms, o_recs + nsess * SRTP_MAX_STREAMS *
-				   sizeof(struct sgpu_rtp_rec));
+		err = tab_reserve(w, &tab);
 	if (!err)
-		err = pool_reserve(w, &w->mscr, down);
-	if (!err)
-		err = pool_reserve(w, &w->bp, BP_HEAD +
-				   al256((size_t)nb * cap * 16) + al256(na * 4));
+		err = bp_take(w, n, nsess, &g, BP_TABLE, stream, &P);
 	if (err)
 		return err;
-	toff_h = (uint32_t *)(w->ms.h + o_toff);
+	toff_h = (uint32_t *)(w->ms.h + tab.o_toff);
 	t[0] = times ? now_ms() : 0;
 	if (msplan_gather(sessv, nsess, toff_h,
-			  (struct sgpu_rtp_rec *)(w->ms.h + o_recs),
+			  (struct sgpu_rtp_rec *)(w->ms.h + tab.o_recs),
 			  (uint32_t *)w->ms.h))
 		return -1;
-	up = o_recs + (size_t)toff_h[nsess] * sizeof(struct sgpu_rtp_rec);
+	up = tab.o_recs + (size_t)toff_h[nsess] * sizeof(struct sgpu_rtp_rec);
 	t[1] = times ? now_ms() : 0;
-	if (w->bp_d != w->bp.d) {
-		/* a new pool (or a call that did not finish): counters from
-		 * zero */
-		err = sgpu_memset(w->bp.d, 0, BP_HEAD, stream);
-		if (err)
-			return err;
-		w->bp_d = w->bp.d;
-	}
 	po = (struct sgpu_plan_out *)w->pl.h;
 	po_d = (struct sgpu_plan_out *)w->pl.d;
 	memset(&R, 0, sizeof(R));
-	B->n = (uint32_t)n;
-	B->nsess = (uint32_t)nsess;
-	B->prot = (uint32_t)prot;
-	B->tag = T;
-	B->need = prot ? (gcm ? 16u : (T > 4 ? T : 4u)) : 0u;
-	B->maxlen = SGPU_CACHED_MAX(c0->mode);
-	B->bshift = bshift;
-	B->nb = nb;
-	B->cap = cap;
-	B->delta = prot ? (int32_t)T : -(int32_t)T;
-	B->gcm = (uint32_t)gcm;
-	B->pos = d->pos;
-	B->end = d->end;
-	B->capv = d->cap;
-	B->sess = d->sess;
-	B->posw = d->pos;
-	B->endw = d->end;
-	B->err = d->err;
-	B->es = L.es;
-	B->hdr = L.hdr;
-	B->desc = L.desc;
-	B->ticket = (uint32_t *)w->bp.d;
-	B->obins = (uint32_t *)(w->bp.d + 64);
-	B->bcount = (uint32_t *)(w->bp.d + 512);
-	B->tmp = (void *)(w->bp.d + BP_HEAD);
-	B->afail = (uint32_t *)(w->bp.d + BP_HEAD + al256((size_t)nb * cap * 16));
+	bplan_fill(B, prot, c0, d, nsess, &L, &g, &P, w->pl.d);
 	B->cm = (const uint32_t *)w->ms.d;
-	B->out = po_d;
-	B->fo = (struct sgpu_fold_out *)(w->pl.d + foff);
-	B->nfail = L.nfail;
 	B->outbytes = (uint32_t)offsetof(struct sgpu_plan_out, tail_ix);
 	B->outh = g_env.nopost ? NULL : (uint32_t *)po;
-	R.toff = (const uint32_t *)(w->ms.d + o_toff);
-	R.recs = (const struct sgpu_rtp_rec *)(w->ms.d + o_recs);
+	R.toff = (const uint32_t *)(w->ms.d + tab.o_toff);
+	R.recs = (const struct sgpu_rtp_rec *)(w->ms.d + tab.o_recs);
 	R.sinfo = (uint32_t *)w->mscr.d;
-	R.sout = (struct sgpu_rtp_rec *)(w->mscr.d + o_sout);
+	R.sout = (struct sgpu_rtp_rec *)(w->mscr.d + tab.o_sout);
 	srv_stop(w);
 	err = sgpu_memcpy_h2d(w->ms.d, w->ms.h, up, stream);
 	if (!err)
@@ -2859,16 +2776,13 @@ int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
 	if (!err && g_env.nopost)
 		err = sgpu_memcpy_d2h(po, po_d, B->outbytes, stream);
 	if (!err)
-		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, down, stream);
+		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, tab.down, stream);
 	t[2] = times ? now_ms() : 0;
 	if (!err)
 		err = sgpu_stream_sync(stream);
 	t[3] = times ? now_ms() : 0;
-	if (err) {
-		sgpu_stream_sync(stream);       /* no copy still reads ms.h */
-		w->bp_d = NULL;
-		return err;
-	}
+	if (err)
+		return bp_failed(err, w, stream);
 	if (po->fail) {
 		/* the crypto launch and the results did nothing */
 		if (!counted)
@@ -2886,14 +2800,12 @@ int dev_msplanned(int op, struct srtp **sessv, size_t nsess,
 		count(&g_cnt_misses, po->nfail);
 		count(&g_cnt_folds, 1);
 		C.undo = 1;
-		err = run_classes(d->arena, d->arena_size, C, c0, po_d, 0, stream);
-		if (!err)
-			err = sgpu_stream_sync(stream);
-		return err ? err : -1;
+		return undo_synced(run_classes(d->arena, d->arena_size, C, c0,
+					       po_d, 0, stream), stream);
 	}
 	count(&g_cnt_msplans, 1);
 	msplan_apply(sessv, nsess, prot, (const uint32_t *)w->mscr.h,
-		     (const struct sgpu_rtp_rec *)(w->mscr.h + o_sout));
+		     (const struct sgpu_rtp_rec *)(w->mscr.h + tab.o_sout));
 	if (times)
 		fprintf(stderr, "re_srtp msplan n=%zu nsess=%zu %s: gather "
 			"%.3f submit %.3f wait %.3f apply %.3f ms\n", n, nsess,
@@ -2925,105 +2837,59 @@ int msrx_eligible(int op, uint32_t pfail)
  * 0: done; -1: not settled, or a forged packet (undone) -- nothing modified,
  * the caller's fallback continues; errno.
  *
- * w->ms, w->mscr as in dev_msplanned; w->bp: BP_HEAD | bucket entries | fail
- * words | per-bucket counts | verdict bytes; w->pl: plan out | fold out
- * (unused) | sgpu_bprx_out.
+ * w->ms, w->mscr: struct tab_layout, as dev_msplanned left them; w->bp:
+ * BP_TABLE_RX (bp_layout.h); w->pl: plan out | fold out (unused) |
+ * sgpu_bprx_out.
  */
 int dev_msrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 {
 	const struct comp *c0 = &sessv[0]->rtp;
 	const int gcm = c0->mode == SGPU_MODE_GCM;
-	const uint32_t T = gcm ? 16u : c0->tag_len;
 	const size_t n = d->n;
-	const size_t na = (n + SGPU_BP_BLOCK * SGPU_BP_PPT - 1) /
-			  (SGPU_BP_BLOCK * SGPU_BP_PPT);
-	const size_t o_toff = al256(nsess * 4);
-	const size_t o_recs = o_toff + al256((nsess + 1) * 4);
-	const size_t o_sout = al256(nsess * 4);
-	const size_t down = o_sout +
-			    nsess * SRTP_MAX_STREAMS * sizeof(struct sgpu_rtp_rec);
-	const size_t roff = (sizeof(struct sgpu_plan_out) + 63) & ~(size_t)63;
+	const struct tab_layout tab =
+		tab_layout(nsess, sizeof(struct sgpu_rtp_rec));
 	const struct ws_sizes z = {
 		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
-		.vs = n * 5 + 64, .cm = 4, .pl = roff + 128, .es = n * 4};
+		.vs = n * 5 + 64, .cm = 4, .pl = PL_FOFF + 128, .es = n * 4};
 	struct ws_layout L;
+	struct bgeo g;
+	struct bp_ptrs P;
 	struct sgpu_bplan_rtps_rx R;
 	struct sgpu_bplan *B = &R.s.b;
 	struct sgpu_compact C;
 	struct sgpu_plan_out *po, *po_d;
 	const struct sgpu_bprx_out *ro;
-	uint32_t bshift, nb, cap;
-	size_t o_afail, o_cnt, o_rs;
 	void *stream = d->stream;
 	struct ws *w;
 	int err;
 
-	if (sgpu_bplan_geometry((uint32_t)n, (uint32_t)nsess, &bshift, &nb, &cap))
+	if (bgeo_get(n, nsess, &g))
 		return -1;
 	w = ws_get();
 	if (!w)
 		return ENOMEM;
-	/* the upload must be the one dev_msplanned made: never a new pool */
-	if (w->ms.cap < o_recs + nsess * SRTP_MAX_STREAMS *
-			 sizeof(struct sgpu_rtp_rec) || w->mscr.cap < down)
+	if (!tab_uploaded(w, &tab))
 		return -1;
-	o_afail = BP_HEAD + al256((size_t)nb * cap * 16);
-	o_cnt = o_afail + al256(na * 4);
-	o_rs = o_cnt + al256((size_t)nb * 8);
 	err = ws_layout_reserve(w, n, &z, &L);
 	if (!err)
-		err = pool_reserve(w, &w->bp, o_rs + al256(n));
+		err = bp_take(w, n, nsess, &g, BP_TABLE_RX, stream, &P);
 	if (err)
 		return err;
-	if (w->bp_d != w->bp.d) {
-		/* a new pool (or a call that did not finish): counters from
-		 * zero */
-		err = sgpu_memset(w->bp.d, 0, BP_HEAD, stream);
-		if (err)
-			return err;
-		w->bp_d = w->bp.d;
-	}
 	po = (struct sgpu_plan_out *)w->pl.h;
 	po_d = (struct sgpu_plan_out *)w->pl.d;
-	ro = (const struct sgpu_bprx_out *)(w->pl.h + roff + 64);
+	ro = (const struct sgpu_bprx_out *)(w->pl.h + PL_FOFF + 64);
 	memset(&R, 0, sizeof(R));
-	B->n = (uint32_t)n;
-	B->nsess = (uint32_t)nsess;
-	B->tag = T;
-	B->maxlen = SGPU_CACHED_MAX(c0->mode);
-	B->bshift = bshift;
-	B->nb = nb;
-	B->cap = cap;
-	B->delta = -(int32_t)T;
-	B->gcm = (uint32_t)gcm;
-	B->pos = d->pos;
-	B->end = d->end;
-	B->capv = d->cap;
-	B->sess = d->sess;
-	B->posw = d->pos;
-	B->endw = d->end;
-	B->err = d->err;
-	B->es = L.es;
-	B->hdr = L.hdr;
-	B->desc = L.desc;
-	B->ticket = (uint32_t *)w->bp.d;
-	B->obins = (uint32_t *)(w->bp.d + 64);
-	B->bcount = (uint32_t *)(w->bp.d + 512);
-	B->tmp = (void *)(w->bp.d + BP_HEAD);
-	B->afail = (uint32_t *)(w->bp.d + o_afail);
+	bplan_fill(B, 0, c0, d, nsess, &L, &g, &P, w->pl.d);
 	B->cm = (const uint32_t *)w->ms.d;
-	B->out = po_d;
-	B->fo = (struct sgpu_fold_out *)(w->pl.d + roff);
-	B->nfail = L.nfail;
-	B->outbytes = (uint32_t)(roff + 64 + sizeof(struct sgpu_bprx_out));
+	B->outbytes = (uint32_t)(PL_FOFF + 64 + sizeof(struct sgpu_bprx_out));
 	B->outh = g_env.nopost ? NULL : (uint32_t *)po;
-	R.s.toff = (const uint32_t *)(w->ms.d + o_toff);
-	R.s.recs = (const struct sgpu_rtp_rec *)(w->ms.d + o_recs);
+	R.s.toff = (const uint32_t *)(w->ms.d + tab.o_toff);
+	R.s.recs = (const struct sgpu_rtp_rec *)(w->ms.d + tab.o_recs);
 	R.s.sinfo = (uint32_t *)w->mscr.d;
-	R.s.sout = (struct sgpu_rtp_rec *)(w->mscr.d + o_sout);
-	R.cnt = (uint32_t *)(w->bp.d + o_cnt);
-	R.rs = w->bp.d + o_rs;
-	R.ro = (struct sgpu_bprx_out *)(w->pl.d + roff + 64);
+	R.s.sout = (struct sgpu_rtp_rec *)(w->mscr.d + tab.o_sout);
+	R.cnt = P.cnt;
+	R.rs = P.rs;
+	R.ro = (struct sgpu_bprx_out *)(w->pl.d + PL_FOFF + 64);
 	R.lookback = RX_LOOKBACK;
 	R.hmac = !gcm;
 	srv_stop(w);
@@ -3045,14 +2911,11 @@ int dev_msrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 	if (!err && g_env.nopost)
 		err = sgpu_memcpy_d2h(po, po_d, B->outbytes, stream);
 	if (!err)
-		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, down, stream);
+		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, tab.down, stream);
 	if (!err)
 		err = sgpu_stream_sync(stream);
-	if (err) {
-		sgpu_stream_sync(stream);
-		w->bp_d = NULL;
-		return err;
-	}
+	if (err)
+		return bp_failed(err, w, stream);
 	if (po->fail) {
 		/* the crypto launch and the results did nothing (the rejection
 		 * was counted: dev_msplanned's, or the bucket planner's) */
@@ -3067,15 +2930,13 @@ int dev_msrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 		count(&g_cnt_misses, po->nfail);
 		count(&g_cnt_folds, 1);
 		C.undo = 1;
-		err = run_classes(d->arena, d->arena_size, C, c0, po_d, 0, stream);
-		if (!err)
-			err = sgpu_stream_sync(stream);
-		return err ? err : -1;
+		return undo_synced(run_classes(d->arena, d->arena_size, C, c0,
+					       po_d, 0, stream), stream);
 	}
 	count(&g_cnt_msrxplans, 1);
 	count(&g_cnt_rxlate, ro->nlate);
 	count(&g_cnt_rxdups, ro->ndup);
 	msplan_apply(sessv, nsess, 0, (const uint32_t *)w->mscr.h,
-		     (const struct sgpu_rtp_rec *)(w->mscr.h + o_sout));
+		     (const struct sgpu_rtp_rec *)(w->mscr.h + tab.o_sout));
 	return 0;
 }

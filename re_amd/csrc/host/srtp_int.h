@@ -285,9 +285,10 @@ struct ws {
 	struct sgpu_srv_mb *srv_mb;
 	struct sgpu_srv_bc *srv_bc;
 	int srv_on;
-	/* multi-session batches of the bucket planner (plan_buckets.hip,
-	 * batch_dev.c dev_bplanned_issue): its counters are zero between
-	 * calls once bp.d has been zeroed (bp_d) */
+	/* multi-session batches of the bucket planners (plan_buckets*.hip),
+	 * laid out by bp_layout.h, handed out by batch_dev.c bp_take: the
+	 * counters in its head are zero between calls once bp.d has been
+	 * zeroed (bp_d) */
 	struct pool bp;
 	uint8_t *bp_d;
 };

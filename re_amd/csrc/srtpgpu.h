@@ -696,8 +696,6 @@ struct sgpu_bplan {
 };
 /* the geometry's target of expected entries per bucket (0: SGPU_BP_EXP) */
 void sgpu_bplan_set_exp(uint32_t e);
-size_t sgpu_bplan_scratch(uint32_t n, uint32_t nsess, uint32_t nb,
-			  uint32_t cap);
 /* geometry for n packets over nsess sessions: 0 and bshift/nb/cap, or -1
  * (the bucket planner does not take the batch) */
 int   sgpu_bplan_geometry(uint32_t n, uint32_t nsess, uint32_t *bshift,
