@@ -41,6 +41,17 @@ int srtcp_decrypt_mbufs(struct srtp *srtp, struct mbuf **mbv, int *errv,
  * packets use sessv[0]).  stream: hipStream_t or NULL (default stream).
  * Returns 0 if the batch ran (per-packet results in err[]), else an errno
  * (EINVAL for bad arguments, EIO for a HIP failure).
+ *
+ * The sessions of one call may use different suites, and, for SRTCP,
+ * different SRTP_UNENCRYPTED_SRTCP (a bridge whose endpoints negotiated
+ * AES-CM-128, AES-256-CM and GCM): every packet is processed with its own
+ * session's keys, tag length and E bit, and the results are those of the
+ * per-packet calls in array order.  Such a call is completed by the general
+ * engine, one launch per kernel class, not by a device planner: the
+ * planners take session arrays of one suite (and one E bit) only, so their
+ * counters do not move and nothing counts as rejected.  The same holds for
+ * struct srtp_batch_dev and the asynchronous entries, where such a call
+ * completes before it returns.
  */
 struct srtp_batch {
 	uint8_t *arena;

@@ -229,11 +229,20 @@ static int batch_async(int op, struct srtp **sessv, size_t nsess,
 		table_unlock();
 		if (err == -1) {
 			tk_drain();
+			/* a many-session gather that declined has marked the
+			 * sessions it visited before as pending behind this
+			 * call's sequence number (mplan_gather_part): the call
+			 * completes here, so the number counts as used and, when
+			 * the call returns, completed -- or those sessions stay
+			 * busy for every other thread (sess_busy) until this
+			 * thread completes some later queued call */
+			t_tk_seq = t_tk_done = t->seq;
 			table_rdlock();
 			err = sess_host(sessv, nsess);
 			if (!err)
 				err = run_dev(op, sessv, nsess, d);
 			table_unlock();
+			__atomic_store_n(&t_own->done, t->seq, __ATOMIC_RELEASE);
 		}
 		t->kind = TK_DONE;
 		t->result = err;
