@@ -211,14 +211,14 @@ COUNTERS = ("fused", "lplans", "dplans", "mplans", "rejects", "devfolds",
             "folds", "rxplans", "mrxplans")
 
 
-def counted(torch, call, knobs, *args):
+def counted(torch, call, knobs, *args, names=COUNTERS):
     """call(*args) under the knobs: (its result, the counters it moved)"""
     # every call from the same first-batch hint (tests/test_gpu_fused.py)
     P.lib().srtp_gpu_tune(b"freshmulti", 0)
-    c0 = {c: P.counter(c) for c in COUNTERS}
+    c0 = {c: P.counter(c) for c in names}
     with P.tune(**knobs):
         out = call(torch, *args)
-    return out, {c: P.counter(c) - c0[c] for c in COUNTERS}
+    return out, {c: P.counter(c) - c0[c] for c in names}
 
 
 def one_stream_paths(suite):
