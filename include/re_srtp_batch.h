@@ -304,7 +304,13 @@ int srtp_alloc_many(struct srtp **srtpv, size_t n, enum srtp_suite suite,
  * not the many-session SRTCP planner; the SRTCP receive planner is off with
  * it), "nomrrxplan" (such an SRTCP unprotect batch whose plan was rejected
  * for reordered or replayed packets inside some stream goes straight to the
- * host engine, not to the SRTCP receive planner), "nomsplan" (an RTP batch
+ * host engine, not to the SRTCP receive planner), "mrfold" (off by default:
+ * a many-session SRTCP unprotect batch on device windows whose device plan,
+ * in-order or receive, was accepted and then met packets whose tag does not
+ * verify is settled on the device -- EAUTH on those packets, the replay rule
+ * over the authentic ones alone -- where it is otherwise undone and folded by
+ * the host engine; the results and states are the same either way),
+ * "nomsplan" (an RTP batch
  * over many
  * sessions on device windows whose sessions hold, or gain in the batch,
  * several SSRCs goes through the host engine, not the many-session
@@ -360,7 +366,13 @@ int srtp_gpu_tune(const char *name, long value);
  * duplicated or replayed, completed by the SRTCP receive planner behind a
  * rejected in-order plan; "rxlate" and "rxdups" count its packets too,
  * "mrplans" does not move for them and "rejects" moves once; srtp_gpu_tune
- * "nomrrxplan" sends them through the host engine), "srxplans" (unprotect
+ * "nomrrxplan" sends them through the host engine), "mrfolds" (SRTCP
+ * unprotect batches over many sessions with forged packets that were settled
+ * on the device under srtp_gpu_tune "mrfold": "misses" counts the forged
+ * packets, "mrplans" / "mrrxplans" / "rejects" move as for the same batch
+ * without them, "folds" does not move; a batch the settlement declines -- a
+ * possible copy older than the look-back -- is undone and folded by the host
+ * engine as without the knob, "folds" +1), "srxplans" (unprotect
  * batches of one session over up to 8 SSRCs whose streams arrived reordered,
  * with gaps, duplicated or replayed, completed by the per-stream receive
  * planner behind a rejected per-stream plan; "rxlate" and "rxdups" count its

@@ -23,6 +23,8 @@
  * SRTCP, many sessions
  *  dev_mplanned_rtcp plan_buckets_rtcp.hip            table     sync only
  *  dev_mrrxplanned   plan_buckets_rtcp_rx.hip         table     sync only
+ *  (mrfold_settle     plan_buckets_rtcp_fold.hip: behind either, a batch with
+ *                     forged packets under srtp_gpu_tune mrfold)
  *
  * state: where the plan reads the stream states -- host: passed in with the
  * launch; resident: the table in HBM (sgpu_sst_*); table: the host's stream
@@ -1808,6 +1810,122 @@ static int tab_uploaded(const struct ws *w, const struct tab_layout *t)
 	return w->ms.cap >= t->up_max && w->mscr.cap >= t->down;
 }
 
+/* ---- SRTCP, many sessions: forged packets settled on the device --------- */
+
+/*
+ * srtp_gpu_tune mrfold: a many-session SRTCP unprotect batch whose plan (R0:
+ * dev_mplanned_rtcp's or dev_mrrxplanned's, as its scatter takes it) was
+ * accepted and whose crypto launch C then counted nfail tag misses, behind
+ * that call's synchronisation.  The verdict bytes of C are final, so nothing
+ * is undone: HMAC suites run the scatter again, sgpu_bplan_rtcp_fold_settle
+ * (the replay rule over the authentic arrivals alone), the keystream over the
+ * packets the plan took for EALREADY and the settle accepts (C with undo = 1
+ * and the settle's bytes for its verdicts), sgpu_bplan_rtcp_fold_finish, one
+ * copy back of the touched tables; GCM suites, which keep no SRTCP replay
+ * window, the results alone on the plan's own tables.  One synchronisation,
+ * the apply (mrplan_apply).
+ * 0: settled (misses += nfail, mrfolds +1); -1: the settle met a possible copy
+ * older than the look-back -- the batch undone as without the knob, the host
+ * engine folds (folds +1); errno.
+ *
+ * w->ms, w->mscr: struct tab_layout, as the plan left them; w->bp:
+ * BP_TABLE_RX (bp_layout.h); w->pl: plan out | sgpu_bprx_out.
+ */
+static int mrfold_settle(struct srtp **sessv, size_t nsess,
+			 struct srtp_batch_dev *d, struct ws *w,
+			 const struct ws_layout *L, const struct bgeo *g,
+			 const struct tab_layout *tab,
+			 const struct sgpu_bplan_rtcp *R0, struct sgpu_compact C,
+			 uint32_t nfail)
+{
+	const struct comp *c0 = &sessv[0]->rtcp;
+	const size_t n = d->n;
+	struct sgpu_plan_out *po = (struct sgpu_plan_out *)w->pl.h;
+	struct sgpu_plan_out *po_d = (struct sgpu_plan_out *)w->pl.d;
+	const struct sgpu_bprx_out *ro =
+		(const struct sgpu_bprx_out *)(w->pl.h + PL_FOFF);
+	struct sgpu_bplan_rtcp_fold F;
+	struct sgpu_bplan_rtcp *R = &F.x.r;
+	struct sgpu_compact K = C;
+	struct bp_ptrs P;
+	void *stream = d->stream;
+	int err;
+
+	memset(&F, 0, sizeof(F));
+	F.vd = L->verdict;
+	F.posw = d->pos;
+	if (c0->mode == SGPU_MODE_GCM) {
+		*R = *R0;
+		err = sgpu_bplan_rtcp_fold_gcm(&F, stream);
+		if (!err)
+			err = sgpu_stream_sync(stream);
+		if (err)
+			return bp_failed(err, w, stream);
+		goto settled;
+	}
+	if (w->pl.cap < PL_FOFF + sizeof(struct sgpu_bprx_out))
+		return EINVAL;          /* (the routes reserve it: never) */
+	err = bp_take(w, n, nsess, g, BP_TABLE_RX, stream, &P);
+	if (err)
+		return err;
+	brtcp_fill(R, 0, sessv[0], d, nsess, L, g, &P, w->pl.d);
+	R->toff = R0->toff;
+	R->recs = R0->recs;
+	R->sinfo = R0->sinfo;
+	R->sout = R0->sout;
+	R->outbytes = (uint32_t)(PL_FOFF + sizeof(struct sgpu_bprx_out));
+	R->outh = g_env.nopost ? NULL : (uint32_t *)po;
+	F.x.cnt = P.cnt;
+	F.x.rs = P.rs;
+	F.x.ro = (struct sgpu_bprx_out *)(w->pl.d + PL_FOFF);
+	F.x.lookback = RX_LOOKBACK;
+	{
+		/* the scatter as the in-order plan launched it */
+		struct sgpu_bplan_rtcp S = *R;
+		S.outbytes = (uint32_t)offsetof(struct sgpu_plan_out, tail_ix);
+		err = sgpu_bplan_rtcp_scatter(d->arena, d->arena_size, &S, stream);
+	}
+	if (!err)
+		err = sgpu_bplan_rtcp_fold_settle(&F, stream);
+	/* the keystream over the packets the settle names, guarded by it */
+	K.undo = 1;
+	K.verdict = P.rs;
+	K.guard = &po_d->fail;
+	if (!err)
+		err = sgpu_run_compact(d->arena, d->arena_size, &K, c0->mode,
+				       (int)c0->nr, 2, 0, stream);
+	if (!err)
+		err = sgpu_bplan_rtcp_fold_finish(&F, stream);
+	if (!err && g_env.nopost)
+		err = sgpu_memcpy_d2h(po, po_d, R->outbytes, stream);
+	if (!err)
+		err = sgpu_memcpy_d2h(w->mscr.h, w->mscr.d, tab->down, stream);
+	if (!err)
+		err = sgpu_stream_sync(stream);
+	if (err)
+		return bp_failed(err, w, stream);
+	if (po->fail) {
+		/* declined: the packets, desc and the verdict bytes are as C left
+		 * them (the keystream launch and the results did nothing); undo
+		 * on the device, fold on the host engine */
+		if (g_env.times)
+			fprintf(stderr, "re_srtp mrfold n=%zu nsess=%zu: not "
+				"settled (SPF %#x)\n", n, nsess, po->fail);
+		count(&g_cnt_misses, nfail);
+		count(&g_cnt_folds, 1);
+		C.guard = NULL;         /* (the plan's: it held) */
+		return undo_synced(undo_rtcp(d, C, c0), stream);
+	}
+	count(&g_cnt_rxlate, ro->nlate);
+	count(&g_cnt_rxdups, ro->ndup);
+settled:
+	count(&g_cnt_misses, nfail);
+	count(&g_cnt_mrfolds, 1);
+	mrplan_apply(sessv, nsess, 0, (const uint32_t *)w->mscr.h,
+		     (const struct sgpu_rtcp_rec *)(w->mscr.h + tab->o_sout));
+	return 0;
+}
+
 /* ---- SRTCP, many sessions with up to 8 SSRCs each ---------------------- */
 
 /*
@@ -1821,7 +1939,8 @@ static int tab_uploaded(const struct ws *w, const struct tab_layout *t)
  * rejected plan's SPF_* bits (0 otherwise).
  * 0: done; -1: a batch the geometry or the gather does not take (nothing
  * counted), a rejected plan, or a forged packet (undone) -- nothing
- * modified, the caller's fallback continues; errno.
+ * modified, the caller's fallback continues; errno.  With srtp_gpu_tune
+ * mrfold an unprotect batch with forged packets goes to mrfold_settle.
  *
  * w->ms, w->mscr: struct tab_layout; w->bp: BP_TABLE (bp_layout.h).
  */
@@ -1837,7 +1956,10 @@ int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 	const struct ws_sizes z = {
 		.hd = n * sizeof(struct sgpu_hdr), .dsc = n * 8,
 		.vs = n * 5 + 64, .cm = 4,
-		.pl = sizeof(struct sgpu_plan_out) + 64, .es = n * 4};
+		/* (mrfold: room for the settle's sgpu_bprx_out) */
+		.pl = g_env.mrfold ? PL_FOFF + 64
+				   : sizeof(struct sgpu_plan_out) + 64,
+		.es = n * 4};
 	struct ws_layout L;
 	struct bgeo g;
 	struct bp_ptrs P;
@@ -1921,6 +2043,10 @@ int dev_mplanned_rtcp(int op, struct srtp **sessv, size_t nsess,
 		return -1;
 	}
 	count(&g_cnt_mrplans, 1);
+	if (po->nfail && g_env.mrfold && !prot && w->pl.cap >= PL_FOFF + 64)
+		/* forged packets, settled on the device */
+		return mrfold_settle(sessv, nsess, d, w, &L, &g, &tab, &R, C,
+				     po->nfail);
 	if (po->nfail) {
 		/* a forged packet: undo on the device (no result was written,
 		 * the host's tables are as they were), fold on the host engine */
@@ -1960,7 +2086,8 @@ int mrrx_eligible(int op, const struct srtp *s, uint32_t pfail)
  * EALREADY packet: MAC only), sgpu_bplan_rtcp_rx_finish, one copy back of the
  * touched tables, one synchronisation, the apply (mrplan_apply).
  * 0: done; -1: not settled, or a forged packet (undone) -- nothing modified,
- * the caller's fallback continues; errno.
+ * the caller's fallback continues; errno.  With srtp_gpu_tune mrfold a batch
+ * with forged packets goes to mrfold_settle.
  *
  * w->ms, w->mscr: struct tab_layout, as dev_mplanned_rtcp left them; w->bp:
  * BP_TABLE_RX (bp_layout.h); w->pl: plan out | sgpu_bprx_out.
@@ -2054,6 +2181,10 @@ int dev_mrrxplanned(struct srtp **sessv, size_t nsess, struct srtp_batch_dev *d)
 		return -1;
 	}
 	count(&g_cnt_mrrxplans, 1);
+	if (po->nfail && g_env.mrfold)
+		/* forged packets, settled on the device */
+		return mrfold_settle(sessv, nsess, d, w, &L, &g, &tab, R, C,
+				     po->nfail);
 	if (po->nfail) {
 		/* a forged packet: undo on the device (no result was written,
 		 * the host's tables are as they were), fold on the host engine */

@@ -44,7 +44,9 @@ enum bp_parts {
 			 BP_CNT | BP_RS,
 	/* the host's stream tables (dev_msplanned, dev_mplanned_rtcp) */
 	BP_TABLE = BP_TMP | BP_AFAIL,
-	/* ... their receive routes (dev_msrxplanned, dev_mrrxplanned) */
+	/* ... their receive routes (dev_msrxplanned, dev_mrrxplanned), and the
+	 * settle of forged SRTCP packets behind either SRTCP route
+	 * (mrfold_settle) */
 	BP_TABLE_RX = BP_TMP | BP_AFAIL | BP_CNT | BP_RS
 };
 

@@ -133,6 +133,10 @@ uint64_t g_cnt_mrrxplans; /* ... reordered / replayed unprotect batches
 				   completed by the receive planner
 				   (plan_buckets_rtcp_rx.hip); rxlate and rxdups
 				   count its packets too */
+uint64_t g_cnt_mrfolds;  /* ... unprotect batches with forged packets
+				   settled on the device behind either plan
+				   (plan_buckets_rtcp_fold.hip, srtp_gpu_tune
+				   mrfold); folds does not move for them */
 uint64_t g_cnt_msplans;  /* many-session RTP device plans over sessions of
 				   several SSRCs (plan_buckets_rtp_streams.hip)
 				   accepted */
@@ -236,6 +240,8 @@ uint64_t srtp_gpu_counter(const char *name)
 		return __atomic_load_n(&g_cnt_mrplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "mrrxplans"))
 		return __atomic_load_n(&g_cnt_mrrxplans, __ATOMIC_RELAXED);
+	if (!strcmp(name, "mrfolds"))
+		return __atomic_load_n(&g_cnt_mrfolds, __ATOMIC_RELAXED);
 	if (!strcmp(name, "msplans"))
 		return __atomic_load_n(&g_cnt_msplans, __ATOMIC_RELAXED);
 	if (!strcmp(name, "msrxplans"))
@@ -345,6 +351,8 @@ int srtp_gpu_tune(const char *name, long value)
 		g_env.nomrplan = value > 0;
 	else if (!strcmp(name, "nomrrxplan"))
 		g_env.nomrrxplan = value > 0;
+	else if (!strcmp(name, "mrfold"))
+		g_env.mrfold = value > 0;
 	else if (!strcmp(name, "nomsplan"))
 		g_env.nomsplan = value > 0;
 	else if (!strcmp(name, "nomsrxplan"))

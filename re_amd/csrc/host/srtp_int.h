@@ -158,6 +158,11 @@ struct srtp_env {
 				   or replayed packets goes straight to the
 				   host engine, not to the receive planner of
 				   plan_buckets_rtcp_rx.hip */
+	int mrfold;             /* srtp_gpu_tune mrfold: a many-session SRTCP
+				   unprotect batch whose accepted plan met
+				   forged packets is settled on the device
+				   (plan_buckets_rtcp_fold.hip), not undone and
+				   folded by the host engine */
 	int smallsync;         /* srtp_gpu_tune smallsync: wait for a small
 				   launch by a stream synchronisation, not
 				   its completion word */
@@ -319,6 +324,7 @@ extern uint64_t g_cnt_dplans, g_cnt_mplans, g_cnt_rplans, g_cnt_lbtimeout;
 extern uint64_t g_cnt_lplans, g_cnt_mrplans, g_cnt_msplans, g_cnt_msrxplans;
 extern uint64_t g_cnt_rxplans, g_cnt_rxlate, g_cnt_rxdups, g_cnt_mrxplans;
 extern uint64_t g_cnt_mrrxplans, g_cnt_srxplans, g_cnt_srplans, g_cnt_srundos;
+extern uint64_t g_cnt_mrfolds;
 extern int g_fresh_multi;       /* srtp.c: the last first batch of a session
 				   showed several SSRCs (see there) */
 extern __thread struct tk_owner *t_own; /* srtp.c: this thread's async

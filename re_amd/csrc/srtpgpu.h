@@ -901,6 +901,45 @@ int   sgpu_bplan_rtcp_rx_finish(const struct sgpu_bplan_rtcp_rx *r,
 				void *stream);
 
 /*
+ * Forged packets of such an UNPROTECT batch settled on the device, behind a
+ * plan of sgpu_bplan_rtcp_plan or sgpu_bplan_rtcp_rx_plan that was accepted
+ * and whose crypto launch counted tag misses (plan_buckets_rtcp_fold.hip; the
+ * rule per (session, SSRC): hip/plan_rtcp_seg_fold.h).  vd are that launch's
+ * verdict bytes, desc the plan's words, toff / recs its upload.  HMAC suites:
+ *   sgpu_bplan_rtcp_scatter      again, unchanged (it zeroes out->fail: the
+ *                                settle's own fail word from here on)
+ *   sgpu_bplan_rtcp_fold_settle  per bucket: slots and ranks as the plans find
+ *                                them, the scan with the forged arrivals
+ *                                masked, per packet rs[] (hip/
+ *                                plan_rtcp_seg_fold.h rsfold_byte: the result,
+ *                                and SV_CIPHERED for an EALREADY packet of the
+ *                                plan that is accepted now), sout / sinfo,
+ *                                cnt[]; an unsettled packet: out->fail |=
+ *   (sgpu_run_compact with undo = 1, verdict = rs and guard = &out->fail: the
+ *   keystream over exactly those packets, per-packet keys)
+ *   sgpu_bplan_rtcp_fold_finish  if !out->fail: end / err (0, EALREADY or
+ *                                EAUTH) per packet, a deciphered packet's desc
+ *                                word; always: bcount back to zero, *ro, and
+ *                                outbytes from out to outh
+ * out->fail after it: nothing changed but rs, sout and sinfo -- the packets,
+ * desc and vd are as the plan's crypto launch left them (undo: as there).
+ * GCM suites keep no SRTCP replay window and the plan's sout / sinfo hold:
+ *   sgpu_bplan_rtcp_fold_gcm     end / err per packet, a forged packet's pos
+ *                                (x.r: in, pos, es, endw, err, delta only)
+ */
+struct sgpu_bplan_rtcp_fold {
+	struct sgpu_bplan_rtcp_rx x;    /* x.rs: out, one byte per packet */
+	const uint8_t *vd;              /* [packet] SV_* of the crypto launch */
+	uint32_t *posw;                 /* = pos (GCM: a forged packet's) */
+};
+int   sgpu_bplan_rtcp_fold_settle(const struct sgpu_bplan_rtcp_fold *f,
+				  void *stream);
+int   sgpu_bplan_rtcp_fold_finish(const struct sgpu_bplan_rtcp_fold *f,
+				  void *stream);
+int   sgpu_bplan_rtcp_fold_gcm(const struct sgpu_bplan_rtcp_fold *f,
+			       void *stream);
+
+/*
  * RTP batches over many sessions with up to 8 SSRCs each, in order per
  * stream, planned on the device behind the bucket planner
  * (plan_buckets_rtp_streams.hip; the rule per (session, SSRC):

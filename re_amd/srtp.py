@@ -602,7 +602,7 @@ def batch_wait(ticket):
 
 def counter(name):
     """srtp_gpu_counter: "misses", "folds", "rejects", the planners'
-    ("mrplans", "mrrxplans", "msplans", "msrxplans", "srplans", "srundos",
+    ("mrplans", "mrrxplans", "mrfolds", "msplans", "msrxplans", "srplans", "srundos",
     "rxlate", "rxdups", ...) since load; 0 for a name the library does not
     know"""
     return int(lib().srtp_gpu_counter(name.encode()))
@@ -611,7 +611,9 @@ def counter(name):
 class tune:
     """srtp_gpu_tune as a context manager: with tune(general=1): ...
     (knobs restored to their defaults on exit; "nosrplan", "nosrxplan",
-    "nomrplan", ...: include/re_srtp_batch.h)"""
+    "nomrplan", ...: include/re_srtp_batch.h).  mrfold=1: forged packets of
+    many-session SRTCP unprotect batches are settled on the device (counter
+    "mrfolds"), not undone and folded by the host engine (counter "folds")"""
 
     def __init__(self, **knobs):
         self.knobs = knobs
