@@ -37,16 +37,19 @@ def rtcp_packet(rng, ssrc, n):
         + rng.integers(0, 256, n, dtype=np.uint8).tobytes()
 
 
-def script(t):
+def script(t, plens=None):
     """thread t's call sequence: (op, packet bytes or index of an earlier
-    protected packet to replay / forge)"""
+    protected packet to replay / forge); plens(rng, t, k): the payload
+    length of the thread's k-th RTP packet (default: below 300 bytes)"""
     rng = np.random.default_rng(100 + t)
+    if plens is None:
+        plens = lambda rng, t, k: int(rng.integers(0, 300))
     ssrc = 0x10000 + t
     out = []
     for k in range(120):
         seq = (65500 + k) & 0xffff
         out.append(("srtp_encrypt", rtp_packet(rng, seq, ssrc,
-                                               plen=int(rng.integers(0, 300)))))
+                                               plen=plens(rng, t, k))))
         out.append(("srtp_decrypt", ("prot", len(out) - 1)))
         if k % 10 == 3:
             out.append(("srtcp_encrypt", rtcp_packet(rng, ssrc, 4 * int(
