@@ -223,6 +223,47 @@ struct rtcp_enc_batch {
  */
 int rtcp_encode_batch_dev(const struct rtcp_enc_batch *b);
 
+/* ---- where report blocks come from ------------------------------------- */
+
+/*
+ * The producers of struct rtcp_enc_rb (and of one RR's struct rtcp_enc_msg
+ * per session) from received RTP: libre's receiver statistics for a batch.
+ * Documented, with struct rtp_rx_sess and the per-packet status values, in
+ * re_rtp_stats_batch.h, which declares them too; they are repeated here so
+ * that this header names the whole C-ABI of the RTCP report path.
+ */
+struct rtp_rx_sess;
+int rtp_rx_stats_batch_dev(const uint8_t *arena, size_t arena_size,
+			   const uint32_t *pos, const uint32_t *end,
+			   const int32_t *res, const uint32_t *sess,
+			   const uint32_t *arrival, size_t n,
+			   struct rtp_rx_sess *sessv, size_t nsess,
+			   int32_t *stat, void *stream);
+int rtp_rx_sr_batch_dev(struct rtp_rx_sess *sessv, size_t nsess,
+			const uint32_t *sess, const uint32_t *ssrc,
+			const uint32_t *ntp_sec, const uint32_t *ntp_frac,
+			const uint32_t *rtp_ts, const uint32_t *psent,
+			const uint32_t *osent, uint64_t recv_ms, size_t n,
+			void *stream);
+int rtp_rx_report_batch_dev(struct rtp_rx_sess *sessv, size_t nsess,
+			    uint64_t now_ms, struct rtcp_enc_rb *rbv,
+			    uint32_t *nrb, const uint32_t *local_ssrc,
+			    struct rtcp_enc_msg *rr_msgv, void *stream);
+int rtp_rx_stats_host(const uint8_t *arena, size_t arena_size,
+		      const uint32_t *pos, const uint32_t *end,
+		      const int32_t *res, const uint32_t *sess,
+		      const uint32_t *arrival, size_t n,
+		      struct rtp_rx_sess *sessv, size_t nsess, int32_t *stat);
+int rtp_rx_sr_host(struct rtp_rx_sess *sessv, size_t nsess,
+		   const uint32_t *sess, const uint32_t *ssrc,
+		   const uint32_t *ntp_sec, const uint32_t *ntp_frac,
+		   const uint32_t *rtp_ts, const uint32_t *psent,
+		   const uint32_t *osent, uint64_t recv_ms, size_t n);
+int rtp_rx_report_host(struct rtp_rx_sess *sessv, size_t nsess,
+		       uint64_t now_ms, struct rtcp_enc_rb *rbv, uint32_t *nrb,
+		       const uint32_t *local_ssrc,
+		       struct rtcp_enc_msg *rr_msgv);
+
 #ifdef __cplusplus
 }
 #endif

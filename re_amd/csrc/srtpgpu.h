@@ -1286,6 +1286,27 @@ int sgpu_rtcp_walk(const uint8_t *arena, uint64_t arena_size,
 		   int32_t *err, uint32_t *stop, void *stream);
 /* rtcp_encode.hip: the batch's packets into its arena (re_rtcp_batch.h) */
 int sgpu_rtcp_encode(const struct rtcp_enc_batch *b);
+/* rtp_stats.hip: receiver statistics (re_rtp_stats_batch.h); all queued on
+ * stream, 0 or ENOMEM / EIO */
+struct rtp_rx_sess;
+struct rtcp_enc_rb;
+struct rtcp_enc_msg;
+int sgpu_rtp_rx_stats(const uint8_t *arena, uint64_t arena_size,
+		      const uint32_t *pos, const uint32_t *end,
+		      const int32_t *res, const uint32_t *sess,
+		      const uint32_t *arrival, uint32_t n,
+		      struct rtp_rx_sess *sessv, uint32_t nsess, int32_t *stat,
+		      void *stream);
+int sgpu_rtp_rx_sr(struct rtp_rx_sess *sessv, uint32_t nsess,
+		   const uint32_t *sess, const uint32_t *ssrc,
+		   const uint32_t *ntp_sec, const uint32_t *ntp_frac,
+		   const uint32_t *rtp_ts, const uint32_t *psent,
+		   const uint32_t *osent, uint64_t recv_ms, uint32_t n,
+		   void *stream);
+int sgpu_rtp_rx_report(struct rtp_rx_sess *sessv, uint32_t nsess,
+		       uint64_t now_ms, struct rtcp_enc_rb *rbv, uint32_t *nrb,
+		       const uint32_t *local_ssrc, struct rtcp_enc_msg *rr_msgv,
+		       void *stream);
 
 #define SGPU_PROF_NAME 48
 void  sgpu_prof_read(double *ms, uint64_t *launches, uint64_t *jobs,

@@ -119,6 +119,8 @@ EXPORTS = (
     "srtp_gpu_prof", "srtp_gpu_prof_read", "srtp_gpu_prof_read_named",
     "srtp_gpu_tune", "srtp_gpu_counter",
     "rtcp_decode_batch_dev",
+    "rtp_rx_stats_batch_dev", "rtp_rx_sr_batch_dev", "rtp_rx_report_batch_dev",
+    "rtp_rx_stats_host", "rtp_rx_sr_host", "rtp_rx_report_host",
     "srtp_udp_alloc", "srtp_udp_recv", "srtp_udp_send", "srtp_udp_stats",
     "srtp_udp_pipeline", "srtp_udp_times",
     "srtp_dtls_key_size", "srtp_keyinfo_split", "srtp_dtls_keying_many",
@@ -193,6 +195,16 @@ def load():
                                              ctypes.c_uint32, vp, vp,
                                              ctypes.c_uint32, vp, vp, vp, vp]
     L.rtcp_encode_batch_dev.argtypes = [ctypes.POINTER(RtcpEncBatch)]
+    u64 = ctypes.c_uint64
+    L.rtp_rx_stats_batch_dev.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp,
+                                         sz, vp, vp]
+    L.rtp_rx_stats_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, sz,
+                                    vp]
+    L.rtp_rx_sr_batch_dev.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp,
+                                      u64, sz, vp]
+    L.rtp_rx_sr_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, u64, sz]
+    L.rtp_rx_report_batch_dev.argtypes = [vp, sz, u64, vp, vp, vp, vp, vp]
+    L.rtp_rx_report_host.argtypes = [vp, sz, u64, vp, vp, vp, vp]
     L.srtp_udp_alloc.argtypes = [ctypes.POINTER(vp), ctypes.c_int, vp, vp,
                                  sz, sz, UDP_RECV_H, vp]
     L.srtp_udp_recv.argtypes = [vp, ctypes.c_int]
@@ -552,6 +564,77 @@ def rtcp_encode_dev(arena_ptr, arena_size, pos_ptr, end_ptr, cap_ptr, n,
                      src_ptr, pool_ptr, nmsg, nrb, nchunk, nsdes, nsrc,
                      pool_size, err_ptr, n, stream)
     return lib().rtcp_encode_batch_dev(ctypes.byref(b))
+
+
+# ---- RTP receiver statistics (include/re_rtp_stats_batch.h) -------------
+# per-packet status beyond 0 / EBADMSG / EINVAL
+RTP_RX_BADSEQ, RTP_RX_NOMEMBER, RTP_RX_SKIPPED = -1, -2, -3
+RTP_RX_MAX_MEMBERS = 8
+RTP_RX_HAS_SOURCE = 1
+
+
+def rtp_rx_dtypes():
+    """numpy layouts of struct rtp_rx_source (88 bytes) and struct
+    rtp_rx_sess (712 bytes); all zero is a fresh session"""
+    import numpy as np
+    src = np.dtype([("ssrc", "<u4"), ("flags", "<u4"), ("max_seq", "<u4"),
+                    ("cycles", "<u4"), ("base_seq", "<u4"),
+                    ("bad_seq", "<u4"), ("received", "<u4"),
+                    ("expected_prior", "<u4"), ("received_prior", "<u4"),
+                    ("transit", "<u4"), ("jitter", "<u4"),
+                    ("last_rtp_ts", "<u4"), ("rx_bytes", "<u8"),
+                    ("sr_recv", "<u8"), ("sr_ntp_hi", "<u4"),
+                    ("sr_ntp_lo", "<u4"), ("sr_rtp_ts", "<u4"),
+                    ("sr_psent", "<u4"), ("sr_osent", "<u4"),
+                    ("reserved", "<u4")])
+    sess = np.dtype([("memberc", "<u4"), ("reserved", "<u4"),
+                     ("m", src, (RTP_RX_MAX_MEMBERS,))])
+    assert src.itemsize == 88 and sess.itemsize == 712
+    return src, sess
+
+
+def rtp_rx_stats(arena_ptr, arena_size, pos_ptr, end_ptr, res_ptr, sess_ptr,
+                 arrival_ptr, n, sessv_ptr, nsess, stat_ptr, stream=None,
+                 host=False):
+    """rtp_rx_stats_batch_dev over device arrays (host=True:
+    rtp_rx_stats_host over host arrays); returns rc"""
+    if host:
+        return lib().rtp_rx_stats_host(arena_ptr, arena_size, pos_ptr,
+                                       end_ptr, res_ptr, sess_ptr,
+                                       arrival_ptr, n, sessv_ptr, nsess,
+                                       stat_ptr)
+    return lib().rtp_rx_stats_batch_dev(arena_ptr, arena_size, pos_ptr,
+                                        end_ptr, res_ptr, sess_ptr,
+                                        arrival_ptr, n, sessv_ptr, nsess,
+                                        stat_ptr, stream)
+
+
+def rtp_rx_sr(sessv_ptr, nsess, sess_ptr, ssrc_ptr, ntp_sec_ptr,
+              ntp_frac_ptr, rtp_ts_ptr, psent_ptr, osent_ptr, recv_ms, n,
+              stream=None, host=False):
+    """rtp_rx_sr_batch_dev / rtp_rx_sr_host; returns rc"""
+    if host:
+        return lib().rtp_rx_sr_host(sessv_ptr, nsess, sess_ptr, ssrc_ptr,
+                                    ntp_sec_ptr, ntp_frac_ptr, rtp_ts_ptr,
+                                    psent_ptr, osent_ptr, recv_ms, n)
+    return lib().rtp_rx_sr_batch_dev(sessv_ptr, nsess, sess_ptr, ssrc_ptr,
+                                     ntp_sec_ptr, ntp_frac_ptr, rtp_ts_ptr,
+                                     psent_ptr, osent_ptr, recv_ms, n,
+                                     stream)
+
+
+def rtp_rx_report(sessv_ptr, nsess, now_ms, rbv_ptr, nrb_ptr,
+                  local_ssrc_ptr=None, rr_msgv_ptr=None, stream=None,
+                  host=False):
+    """rtp_rx_report_batch_dev / rtp_rx_report_host: rbv holds nsess * 8
+    struct rtcp_enc_rb, rr_msgv (optional) nsess struct rtcp_enc_msg;
+    returns rc"""
+    if host:
+        return lib().rtp_rx_report_host(sessv_ptr, nsess, now_ms, rbv_ptr,
+                                        nrb_ptr, local_ssrc_ptr, rr_msgv_ptr)
+    return lib().rtp_rx_report_batch_dev(sessv_ptr, nsess, now_ms, rbv_ptr,
+                                         nrb_ptr, local_ssrc_ptr,
+                                         rr_msgv_ptr, stream)
 
 
 def rtcp_decode_full_dev(arena_ptr, arena_size, pos_ptr, end_ptr, n,
