@@ -34,20 +34,22 @@
  * SGPU_BP_SEGMAX packets in it) fails with SPF_SEG and is re-planned by the
  * radix-sort grouping; any other failed check rejects the plan exactly as
  * the other planners do (nothing modified, the host plans).
+ *
+ * The steps every bucket planner shares -- a bucket's entries in, the segment
+ * starts, the order inside a session, the pinned mirror, the launch checks --
+ * are plan_bucket_common.h's.
  */
-#include <hip/hip_runtime.h>
-#include <errno.h>
-#include <stdio.h>
-#include "../srtpgpu.h"
+#include "plan_bucket_common.h"
 #include "plan_common.h"
+
+/* the header's definition once more, which the compiler holds to it: the
+ * suite reads the bucket planners' workgroup size from this file
+ * (tests/test_gpu_roc.py) */
+#define BPB SGPU_BP_BLOCK
 
 #ifndef EAUTH
 #define EAUTH 217               /* include/re_types.h:215-217 */
 #endif
-
-#define BPB SGPU_BP_BLOCK
-#define BP_IMASK 0x3ffffffu     /* entry: packet index | length bin << 26 */
-#define BP_OBINS 64
 
 /* ---- block-wide scans (1024 threads, 16 waves) ------------------------ */
 
@@ -124,29 +126,6 @@ __device__ __forceinline__ bool bp_last(uint32_t *ticket, uint32_t tbase,
 	}
 	__syncthreads();
 	return *flag != 0;
-}
-
-static_assert(sizeof(struct sgpu_sstate) == 32 &&
-	      offsetof(struct sgpu_sstate, flags) == 12,
-	      "bp_ld/bp_st move the state as two 16-byte words");
-
-__device__ __forceinline__ struct sgpu_sstate bp_ld(const struct sgpu_sstate *p)
-{
-	const uint4 a = ((const uint4 *)p)[0], b = ((const uint4 *)p)[1];
-	struct sgpu_sstate s;
-	s.ssrc = a.x; s.roc = a.y; s.s_l = a.z; s.flags = a.w;
-	s.lix = (uint64_t)b.y << 32 | b.x;
-	s.bitmap = (uint64_t)b.w << 32 | b.z;
-	return s;
-}
-
-__device__ __forceinline__ void bp_st(struct sgpu_sstate *p,
-				      const struct sgpu_sstate &s)
-{
-	((uint4 *)p)[0] = make_uint4(s.ssrc, s.roc, s.s_l, s.flags);
-	((uint4 *)p)[1] = make_uint4((uint32_t)s.lix, (uint32_t)(s.lix >> 32),
-				     (uint32_t)s.bitmap,
-				     (uint32_t)(s.bitmap >> 32));
 }
 
 /* ---- 1: parse, checks, bucket scatter --------------------------------- */
@@ -304,8 +283,6 @@ k_bp_scatter(const uint8_t *__restrict__ arena, uint64_t asz,
 
 /* ---- 2: per bucket, the plan ------------------------------------------ */
 
-#define BP_EPT (SGPU_BP_CAPMAX / BPB)   /* entries per thread, at most */
-
 struct BpPlanLds {
 	uint32_t ent[SGPU_BP_CAPMAX];   /* entry word, arrival order in bucket */
 	uint16_t sq[SGPU_BP_CAPMAX];    /* seq */
@@ -370,29 +347,12 @@ k_bp_plan(const struct sgpu_bplan P)
 	const uint32_t s0 = b << P.bshift;
 	const uint32_t ns = min(1u << P.bshift, P.nsess - s0);
 	const uint32_t EPT = P.cap / BPB;
-	uint32_t m = P.bcount[b];
-	uint32_t f = 0;
-	{
-		/* the scatter workgroups' fail words, spread over the buckets
-		 * (no workgroup waits for another) */
-		const uint32_t na = (P.n + BPB * SGPU_BP_PPT - 1) /
-				    (BPB * SGPU_BP_PPT);
-		for (uint32_t k = b + tid * P.nb; k < na; k += BPB * P.nb)
-			f |= P.afail[k];
-	}
-	if (m > P.cap) {
-		f |= SPF_SEG;           /* (the scatter flagged it too) */
-		m = 0;
-	}
 	/* the bucket's entries (EPT per thread, all in flight): index and
 	 * length bin, seq and session, SSRC, place in the bin */
-	uint4 ev4[BP_EPT];
-#pragma unroll
-	for (int j = 0; j < BP_EPT; j++) {
-		const uint32_t k = tid + j * BPB;
-		ev4[j] = k < m ? P.tmp[(size_t)b * P.cap + k]
-			       : make_uint4(0, 0, 0, 0);
-	}
+	uint4 ev4[BK_EPT];
+	uint32_t m;
+	uint32_t f = bk_entries(P.afail, P.n, P.nb, P.bcount, P.tmp, P.cap, &m,
+				ev4);
 	if (tid == 0)
 		S.bf = 0;
 	if (tid < BP_OBINS)
@@ -403,11 +363,11 @@ k_bp_plan(const struct sgpu_bplan P)
 		const uint32_t s = s0 + tid, slot = P.cm[s] >> 1;
 		struct sgpu_sstate x;
 		if (P.upneed && P.upneed[s]) {
-			x = bp_ld(P.up + s);
-			bp_st(P.sst + slot, x);
+			x = bk_ld(P.up + s);
+			bk_st(P.sst + slot, x);
 		}
 		else {
-			x = bp_ld(P.sst + slot);
+			x = bk_ld(P.sst + slot);
 		}
 		S.st[tid] = x;
 		S.cnt[tid] = 0;
@@ -419,7 +379,7 @@ k_bp_plan(const struct sgpu_bplan P)
 	/* the entries: seq, session, rank in session (the header checks
 	 * were the scatter's) */
 #pragma unroll
-	for (int j = 0; j < BP_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		if (k >= m)
 			continue;
@@ -432,33 +392,10 @@ k_bp_plan(const struct sgpu_bplan P)
 		atomicMax(&S.smax[l], ev4[j].z);
 	}
 	__syncthreads();
-	/* segment starts (sessions, <= 256: wave 0) and the length bins'
-	 * starts in the launch order (64: wave 1) */
-	if (tid < 64) {
-		uint32_t c4[4], v = 0;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			c4[q] = l < ns ? S.cnt[l] : 0u;
-			v += c4[q];
-		}
-		uint32_t x = v;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t u = (uint32_t)__shfl_up((int)x, d);
-			if (tid >= (uint32_t)d)
-				x += u;
-		}
-		uint32_t run = x - v;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			if (l < SGPU_BP_NSB)
-				S.start[l] = run;
-			run += c4[q];
-		}
-	}
-	else if (tid < 128) {
+	/* the sessions' segment starts (wave 0) and the length bins' starts in
+	 * the launch order (64: wave 1) */
+	bk_starts(S.cnt, S.start, ns);
+	if (tid >= 64 && tid < 128) {
 		const uint32_t lane = tid - 64, v = S.bb[lane];
 		uint32_t x = v;
 #pragma unroll
@@ -484,32 +421,18 @@ k_bp_plan(const struct sgpu_bplan P)
 	__syncthreads();
 	const bool dead = S.bf != 0;    /* the plan fails: nothing more */
 	if (!dead) {
-		/* grouped by session; the crypto launch order (descending
-		 * length bins, each scatter workgroup's packets together) */
+		/* the crypto launch order (descending length bins, each scatter
+		 * workgroup's packets together) */
 #pragma unroll
-		for (int j = 0; j < BP_EPT; j++) {
-			const uint32_t k = tid + j * BPB;
-			if (k >= m)
-				continue;
-			const uint32_t i = ev4[j].x & BP_IMASK;
-			S.un[S.start[S.sl[k]] + S.srt[k]] = (uint16_t)k;
-			P.order[S.bb[ev4[j].x >> 26] + ev4[j].w] = i;
+		for (int j = 0; j < BK_EPT; j++) {
+			if (tid + j * BPB < m)
+				P.order[S.bb[ev4[j].x >> 26] + ev4[j].w] =
+					ev4[j].x & BP_IMASK;
 		}
 	}
-	__syncthreads();
-	if (!dead) {
-		/* inside a session by packet index: the stable order the
-		 * reference processes them in */
-		for (uint32_t q = tid; q < m; q += BPB) {
-			const uint32_t e = S.un[q], l = S.sl[e];
-			const uint32_t f0 = S.start[l], c = S.cnt[l];
-			const uint32_t ie = S.ent[e] & BP_IMASK;
-			uint32_t r = 0;
-			for (uint32_t t = f0; t < f0 + c; t++)
-				r += (S.ent[S.un[t]] & BP_IMASK) < ie ? 1u : 0u;
-			S.srt[f0 + r] = (uint16_t)e;
-		}
-	}
+	/* by (session, packet index): the stable order the reference processes
+	 * them in */
+	bk_sort16(m, dead, S.ent, S.sl, S.cnt, S.start, S.un, S.srt);
 	__syncthreads();
 	if (tid < ns && !dead)
 		S.sl0[tid] = (S.st[tid].flags & SST_SL_SET) ? S.st[tid].s_l
@@ -633,7 +556,7 @@ k_bp_plan(const struct sgpu_bplan P)
 		else {
 			P.sseg[s] = 0;
 		}
-		bp_st(P.sout + s, o);
+		bk_st(P.sout + s, o);
 	}
 	if (f)
 		atomicOr(&S.bf, f);
@@ -686,18 +609,6 @@ __device__ __forceinline__ void bp_forged(const struct sgpu_bplan &P,
 	P.err[i] = EAUTH;
 	P.posw[i] += P.hdr[i].hdr_len;
 	P.endw[i] = P.gcm ? P.es[i] : P.es[i] + (uint32_t)P.delta;
-}
-
-/* the call's outcome (plan out, fold out) to the caller's pinned mirror
- * with vector stores, once it is final: no blit copy behind the launch */
-__device__ __forceinline__ void bp_post(const struct sgpu_bplan &P,
-					uint32_t tid)
-{
-	if (!P.outh)
-		return;
-	const uint32_t *src = (const uint32_t *)P.out;
-	for (uint32_t w = tid; w < P.outbytes / 4u; w += BPB)
-		P.outh[w] = src[w];
 }
 
 __global__ void __launch_bounds__(BPB)
@@ -755,16 +666,16 @@ k_bp_finish(const struct sgpu_bplan P)
 	}
 	__syncthreads();
 	if (b == 0 && (fail || !nf))
-		bp_post(P, tid);
+		bk_post(P.out, P.outh, P.outbytes, BK_NOWORD, 0);
 	if (fail || !nf) {
 		/* every tag verified: the touched states replace the resident
 		 * ones (k_sst_commit) */
 		if (!fail && tid < ns) {
 			const uint32_t s = s0 + tid;
-			struct sgpu_sstate o = bp_ld(P.sout + s);
+			struct sgpu_sstate o = bk_ld(P.sout + s);
 			if (o.flags & SST_TOUCHED) {
 				o.flags &= ~(uint32_t)SST_TOUCHED;
-				bp_st(P.sst + (P.cm[s] >> 1), o);
+				bk_st(P.sst + (P.cm[s] >> 1), o);
 			}
 		}
 		return;
@@ -777,7 +688,7 @@ k_bp_finish(const struct sgpu_bplan P)
 		 * s_l than the plan assumed */
 		if (tid < ns) {
 			const uint32_t s = s0 + tid, v = P.sseg[s];
-			S.st[tid] = bp_ld(P.sst + (P.cm[s] >> 1));
+			S.st[tid] = bk_ld(P.sst + (P.cm[s] >> 1));
 			S.f0[tid] = v & 0xffffu;
 			S.cnt[tid] = v >> 16;
 			if (v >> 16)
@@ -848,7 +759,7 @@ k_bp_finish(const struct sgpu_bplan P)
 		if (tid < ns && S.cnt[tid]) {
 			const uint32_t s = s0 + tid, f0 = S.f0[tid];
 			const uint32_t l = f0 + S.cnt[tid] - 1u;
-			struct sgpu_sstate o = bp_ld(P.sout + s);
+			struct sgpu_sstate o = bk_ld(P.sout + s);
 			o.s_l = bf_slv(S, S.ev[l], tid);
 			const struct sgpu_sstate &x = S.st[tid];
 			int32_t j = (int32_t)l;
@@ -869,7 +780,7 @@ k_bp_finish(const struct sgpu_bplan P)
 			}
 			o.lix = w.lix;
 			o.bitmap = w.bitmap;
-			bp_st(P.sout + s, o);
+			bk_st(P.sout + s, o);
 		}
 		if (cf)
 			atomicOr(&S.cf, 1u);
@@ -892,10 +803,10 @@ k_bp_finish(const struct sgpu_bplan P)
 			/* the fold holds: the states and the forged packets'
 			 * results (a fold that fails leaves all to the host) */
 			for (uint32_t s = tid; s < P.nsess; s += BPB) {
-				struct sgpu_sstate o = bp_ld(P.sout + s);
+				struct sgpu_sstate o = bk_ld(P.sout + s);
 				if (o.flags & SST_TOUCHED) {
 					o.flags &= ~(uint32_t)SST_TOUCHED;
-					bp_st(P.sst + (P.cm[s] >> 1), o);
+					bk_st(P.sst + (P.cm[s] >> 1), o);
 				}
 			}
 			if (P.flist) {
@@ -925,7 +836,7 @@ k_bp_finish(const struct sgpu_bplan P)
 			*P.gate = ff ? 1u : 0u;
 	}
 	__syncthreads();
-	bp_post(P, tid);
+	bk_post(P.out, P.outh, P.outbytes, BK_NOWORD, 0);
 }
 
 /* ---- host side ------------------------------------------------------ */
@@ -974,22 +885,9 @@ extern "C" int sgpu_bplan_geometry(uint32_t n, uint32_t nsess,
 
 static int bp_check(const struct sgpu_bplan *b)
 {
-	if (!b->n || b->n > SGPU_BP_NMAX || b->nsess < 2 || !b->nb ||
-	    b->nb > SGPU_BP_NBMAX || b->bshift > 8 || !b->cap ||
-	    b->cap > SGPU_BP_CAPMAX || b->cap % BPB ||
-	    ((uint64_t)b->nb << b->bshift) < b->nsess ||
-	    ((uint64_t)(b->nb - 1) << b->bshift) >= b->nsess)
+	if (bk_geom_bad(b->n, b->nsess, b->nb, b->bshift, b->cap))
 		return EINVAL;
 	return 0;
-}
-
-static int bp_err(const char *what)
-{
-	const hipError_t e = hipGetLastError();
-	if (e == hipSuccess)
-		return 0;
-	fprintf(stderr, "re_srtp: %s launch: %s\n", what, hipGetErrorString(e));
-	return EIO;
 }
 
 extern "C" int sgpu_bplan_scatter(const uint8_t *arena, uint64_t arena_size,
@@ -997,10 +895,9 @@ extern "C" int sgpu_bplan_scatter(const uint8_t *arena, uint64_t arena_size,
 {
 	if (bp_check(b))
 		return EINVAL;
-	const uint32_t g = (b->n + BPB * SGPU_BP_PPT - 1) / (BPB * SGPU_BP_PPT);
-	hipLaunchKernelGGL(k_bp_scatter, dim3(g), dim3(BPB), 0,
+	hipLaunchKernelGGL(k_bp_scatter, dim3(bk_grid(b->n)), dim3(BPB), 0,
 			   (hipStream_t)stream, arena, arena_size, *b);
-	return bp_err("k_bp_scatter");
+	return bk_err("k_bp_scatter");
 }
 
 extern "C" int sgpu_bplan_plan(const struct sgpu_bplan *b, void *stream)
@@ -1009,15 +906,14 @@ extern "C" int sgpu_bplan_plan(const struct sgpu_bplan *b, void *stream)
 		return EINVAL;
 	hipLaunchKernelGGL(k_bp_plan, dim3(b->nb), dim3(BPB), 0,
 			   (hipStream_t)stream, *b);
-	return bp_err("k_bp_plan");
+	return bk_err("k_bp_plan");
 }
 
 extern "C" int sgpu_bplan_finish(const struct sgpu_bplan *b, void *stream)
 {
 	if (bp_check(b))
 		return EINVAL;
-	const uint32_t g = (b->n + BPB * SGPU_BP_PPT - 1) / (BPB * SGPU_BP_PPT);
-	hipLaunchKernelGGL(k_bp_finish, dim3(b->nb + g), dim3(BPB), 0,
+	hipLaunchKernelGGL(k_bp_finish, dim3(b->nb + bk_grid(b->n)), dim3(BPB), 0,
 			   (hipStream_t)stream, *b);
-	return bp_err("k_bp_finish");
+	return bk_err("k_bp_finish");
 }

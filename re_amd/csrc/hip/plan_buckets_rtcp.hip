@@ -31,31 +31,13 @@
  *                  to its pinned mirror
  *
  * No workgroup waits for another.  Any failed check rejects the whole plan:
- * nothing of the caller's is modified and the host plans.
+ * nothing of the caller's is modified and the host plans.  k_bpr_plan's front
+ * (entries, table words, grouping and rank), pass 2's slot and the finish tail
+ * are plan_bucket_common.h's; pass 1 keeps the records in LDS and is its own.
  */
-#include <hip/hip_runtime.h>
-#include <errno.h>
-#include <stdio.h>
-#include "../srtpgpu.h"
-#include "plan_rtcp_seg.h"
+#include "plan_bucket_common.h"
 
-#define BPB SGPU_BP_BLOCK
-#define BPR_EPT (SGPU_BP_CAPMAX / BPB)  /* entries per thread, at most */
-
-static_assert(sizeof(struct rseg_rec) == 16 &&
-	      sizeof(struct sgpu_rtcp_rec) == 16 &&
-	      offsetof(struct sgpu_rtcp_rec, blo) ==
-	      offsetof(struct rseg_rec, blo),
-	      "a stream record moves as one 16-byte word");
 static_assert(RSEG_MAX == 8, "sinfo holds 8 touched bits");
-
-__device__ __forceinline__ struct rseg_rec bpr_ld(const struct sgpu_rtcp_rec *p)
-{
-	const uint4 a = *(const uint4 *)p;
-	struct rseg_rec r;
-	r.ssrc = a.x; r.ix = a.y; r.blo = a.z; r.bhi = a.w;
-	return r;
-}
 
 __device__ __forceinline__ uint32_t bpr_be32(const uint8_t *q)
 {
@@ -183,7 +165,7 @@ k_bpr_scatter(const uint8_t *__restrict__ arena, uint64_t asz,
 /*
  * The bucket in LDS.  The entries are written once in (session, packet
  * index) order, so a look back reads consecutive words; a thread keeps what
- * it learnt about its own (at most BPR_EPT) positions in registers between
+ * it learnt about its own (at most BK_EPT) positions in registers between
  * the passes.
  */
 struct BprLds {
@@ -213,133 +195,43 @@ k_bpr_plan(const struct sgpu_bplan_rtcp P)
 	const uint32_t tid = threadIdx.x, b = blockIdx.x;
 	const uint32_t s0 = b << P.bshift;
 	const uint32_t ns = min(1u << P.bshift, P.nsess - s0);
-	uint32_t m = P.bcount[b];
-	uint32_t f = 0;
-	{
-		/* the scatter workgroups' fail words, spread over the buckets
-		 * (no workgroup waits for another) */
-		const uint32_t na = (in.n + BPB * SGPU_BP_PPT - 1) /
-				    (BPB * SGPU_BP_PPT);
-		for (uint32_t k = b + tid * P.nb; k < na; k += BPB * P.nb)
-			f |= P.afail[k];
-	}
-	if (m > P.cap) {
-		f |= SPF_SEG;           /* (the scatter flagged it too) */
-		m = 0;
-	}
-	uint4 ev4[BPR_EPT];
-#pragma unroll
-	for (int j = 0; j < BPR_EPT; j++) {
-		const uint32_t k = tid + j * BPB;
-		ev4[j] = k < m ? P.tmp[(size_t)b * P.cap + k]
-			       : make_uint4(0, 0, 0, 0);
-	}
+	uint4 ev4[BK_EPT];
+	uint32_t m;
+	uint32_t f = bk_entries(P.afail, in.n, P.nb, P.bcount, P.tmp, P.cap, &m,
+				ev4);
 	if (tid == 0)
 		S.bf = 0;
-	if (tid < ns) {
-		const uint32_t s = s0 + tid;
-		const uint32_t t0 = P.toff[s], t1 = P.toff[s + 1];
-		uint32_t nk = t1 - t0;
-		if (t1 < t0 || nk > RSEG_MAX) {
-			f |= SPF_BAD;   /* (the host builds toff: never) */
-			nk = 0;
-		}
-		S.nk[tid] = nk;
-		S.nst[tid] = nk;
-		S.cnt[tid] = 0;
-		S.tmask[tid] = 0;
-	}
-	for (uint32_t q = tid; q < SGPU_BP_NSB * RSEG_MAX; q += BPB) {
-		(&S.acc[0][0])[q] = 0;
-		(&S.wlo[0][0])[q] = 0;
-		(&S.whi[0][0])[q] = 0;
-	}
+	f |= bk_tables(P.toff, s0, ns, NULL, S.nk, S.nst, S.cnt, S.tmask,
+		       &S.acc[0][0], &S.wlo[0][0], &S.whi[0][0]);
 	__syncthreads();
 	/* the sessions' tables, one record per thread */
 	for (uint32_t q = tid; q < ns * RSEG_MAX; q += BPB) {
 		const uint32_t l = q / RSEG_MAX, x = q % RSEG_MAX;
 		struct rseg_rec r = {0, 0, 0, 0};
 		if (x < S.nk[l])
-			r = bpr_ld(P.recs + P.toff[s0 + l] + x);
+			r = bk_ld(P.recs + P.toff[s0 + l] + x);
 		S.rec[l][x] = r;
 	}
-	/* rank in session (unstable) */
-	uint32_t ru[BPR_EPT];
-#pragma unroll
-	for (int j = 0; j < BPR_EPT; j++) {
-		const uint32_t k = tid + j * BPB;
-		ru[j] = 0;
-		if (k < m)
-			ru[j] = atomicAdd(&S.cnt[ev4[j].y & 0xffu], 1u);
-	}
-	__syncthreads();
-	/* segment starts (sessions, <= 256: wave 0) */
-	if (tid < 64) {
-		uint32_t c4[4], v = 0;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			c4[q] = l < ns ? S.cnt[l] : 0u;
-			v += c4[q];
-		}
-		uint32_t x = v;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t y = (uint32_t)__shfl_up((int)x, d);
-			if (tid >= (uint32_t)d)
-				x += y;
-		}
-		uint32_t run = x - v;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			if (l < SGPU_BP_NSB)
-				S.start[l] = run;
-			run += c4[q];
-		}
-	}
-	if (tid < ns && S.cnt[tid] > SGPU_BP_SEGMAX)
-		f |= SPF_SEG;
-	if (f)
-		atomicOr(&S.bf, f);
+	/* by (session, packet index): the order the reference sees them in */
+	uint32_t pos[BK_EPT];
+	const bool dead = bk_sort(ev4, 0, m, ns, f, S.cnt, S.start, S.gidx, &S.bf,
+				  pos);
 	f = 0;
-	__syncthreads();
-	const bool dead = S.bf != 0;    /* the plan fails: nothing more */
-	if (!dead) {
-		/* grouped by session */
 #pragma unroll
-		for (int j = 0; j < BPR_EPT; j++) {
-			const uint32_t k = tid + j * BPB;
-			if (k < m)
-				S.gidx[S.start[ev4[j].y & 0xffu] + ru[j]] = ev4[j].x;
-		}
-	}
-	__syncthreads();
-	if (!dead) {
-		/* inside a session by packet index: the order the reference
-		 * sees them in */
-#pragma unroll
-		for (int j = 0; j < BPR_EPT; j++) {
-			const uint32_t k = tid + j * BPB;
-			if (k >= m)
-				continue;
-			const uint32_t l = ev4[j].y & 0xffu;
-			const uint32_t f0 = S.start[l], c = S.cnt[l];
-			uint32_t r = 0;
-			for (uint32_t t = f0; t < f0 + c; t++)
-				r += S.gidx[t] < ev4[j].x ? 1u : 0u;
-			S.idx[f0 + r] = ev4[j].x;
-			S.meta[f0 + r] = ev4[j].y;
-			S.ssrc[f0 + r] = ev4[j].z;
-			S.word[f0 + r] = ev4[j].w;
-		}
+	for (int j = 0; j < BK_EPT; j++) {
+		if (dead || tid + j * BPB >= m)
+			continue;
+		S.idx[pos[j]] = ev4[j].x;
+		S.meta[pos[j]] = ev4[j].y;
+		S.ssrc[pos[j]] = ev4[j].z;
+		S.word[pos[j]] = ev4[j].w;
 	}
 	__syncthreads();
 	/* pass 1, per sorted position: the known slot, the look back */
-	uint32_t kn[BPR_EPT];
-	struct rseg_look lk[BPR_EPT];
+	uint32_t kn[BK_EPT];
+	struct rseg_look lk[BK_EPT];
 #pragma unroll
-	for (int j = 0; j < BPR_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		kn[j] = RSEG_NONE;
 		lk[j] = rseg_look_init(k);
@@ -354,19 +246,16 @@ k_bpr_plan(const struct sgpu_bplan_rtcp P)
 	__syncthreads();
 	/* pass 2: the slot; a new stream's record; the stream's packet count
 	 * (protect) or largest index (unprotect) */
-	uint32_t sl[BPR_EPT];
+	uint32_t sl[BK_EPT];
 #pragma unroll
-	for (int j = 0; j < BPR_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		sl[j] = RSEG_NONE;
 		if (dead || k >= m)
 			continue;
 		const uint32_t l = S.meta[k] & 0xffu;
-		uint32_t nnew = 0;
-		if (kn[j] == RSEG_NONE)
-			for (uint32_t t = S.start[l]; t < lk[j].first; t++)
-				nnew += S.opens[t];
-		const uint32_t slot = rseg_slot(kn[j], S.nk[l], nnew);
+		const uint32_t slot = bk_slot(kn[j], lk[j].first, S.start[l],
+					      S.nk[l], S.opens);
 		if (rseg_enosr(slot)) {
 			f |= SPF_SSRC;  /* a 9th stream: ENOSR on the host */
 			continue;
@@ -375,16 +264,15 @@ k_bpr_plan(const struct sgpu_bplan_rtcp P)
 		if (S.opens[k]) {
 			const struct rseg_rec r = {S.ssrc[k], 0, 0, 0};
 			S.rec[l][slot] = r;
-			atomicMax(&S.nst[l], slot + 1u);
 		}
-		atomicOr(&S.tmask[l], 1u << slot);
-		atomicMax(&S.acc[l][slot], in.prot ? lk[j].rank + 1u
-						   : S.word[k] & 0x7fffffffu);
+		bk_touch(l, slot, S.opens[k],
+			 in.prot ? lk[j].rank + 1u : S.word[k] & 0x7fffffffu,
+			 S.nst, S.tmask, &S.acc[l][slot]);
 	}
 	__syncthreads();
 	/* pass 3: the rule, desc, the window bit */
 #pragma unroll
-	for (int j = 0; j < BPR_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		if (dead || k >= m || sl[j] == RSEG_NONE)
 			continue;
@@ -471,23 +359,15 @@ k_bpr_finish(const struct sgpu_bplan_rtcp P)
 	 * plan kernel completed before the crypto launches) */
 	if (tid == 0)
 		P.out->nfail = nf;
-	if (P.outh) {
-		const uint32_t *src = (const uint32_t *)P.out;
-		const uint32_t wn = offsetof(struct sgpu_plan_out, nfail) / 4u;
-		for (uint32_t w = tid; w < P.outbytes / 4u; w += BPB)
-			P.outh[w] = w == wn ? nf : src[w];
-	}
+	bk_post(P.out, P.outh, P.outbytes,
+		offsetof(struct sgpu_plan_out, nfail) / 4u, nf);
 }
 
 /* ---- host side ------------------------------------------------------ */
 
 static int bpr_check(const struct sgpu_bplan_rtcp *r)
 {
-	if (!r->in.n || r->in.n > SGPU_BP_NMAX || r->nsess < 2 || !r->nb ||
-	    r->nb > SGPU_BP_NBMAX || r->bshift > 8 || !r->cap ||
-	    r->cap > SGPU_BP_CAPMAX || r->cap % BPB ||
-	    ((uint64_t)r->nb << r->bshift) < r->nsess ||
-	    ((uint64_t)(r->nb - 1) << r->bshift) >= r->nsess ||
+	if (bk_geom_bad(r->in.n, r->nsess, r->nb, r->bshift, r->cap) ||
 	    !r->pos || !r->end || !r->sess || !r->endw || !r->err || !r->es ||
 	    !r->hdr || !r->desc || !r->tmp || !r->bcount || !r->afail ||
 	    !r->toff || !r->recs || !r->sout || !r->sinfo || !r->out ||
@@ -497,15 +377,6 @@ static int bpr_check(const struct sgpu_bplan_rtcp *r)
 	return 0;
 }
 
-static int bpr_err(const char *what)
-{
-	const hipError_t e = hipGetLastError();
-	if (e == hipSuccess)
-		return 0;
-	fprintf(stderr, "re_srtp: %s launch: %s\n", what, hipGetErrorString(e));
-	return EIO;
-}
-
 extern "C" int sgpu_bplan_rtcp_scatter(const uint8_t *arena,
 				       uint64_t arena_size,
 				       const struct sgpu_bplan_rtcp *r,
@@ -513,11 +384,9 @@ extern "C" int sgpu_bplan_rtcp_scatter(const uint8_t *arena,
 {
 	if (bpr_check(r))
 		return EINVAL;
-	const uint32_t g = (r->in.n + BPB * SGPU_BP_PPT - 1) /
-			   (BPB * SGPU_BP_PPT);
-	hipLaunchKernelGGL(k_bpr_scatter, dim3(g), dim3(BPB), 0,
+	hipLaunchKernelGGL(k_bpr_scatter, dim3(bk_grid(r->in.n)), dim3(BPB), 0,
 			   (hipStream_t)stream, arena, arena_size, *r);
-	return bpr_err("k_bpr_scatter");
+	return bk_err("k_bpr_scatter");
 }
 
 extern "C" int sgpu_bplan_rtcp_plan(const struct sgpu_bplan_rtcp *r,
@@ -527,7 +396,7 @@ extern "C" int sgpu_bplan_rtcp_plan(const struct sgpu_bplan_rtcp *r,
 		return EINVAL;
 	hipLaunchKernelGGL(k_bpr_plan, dim3(r->nb), dim3(BPB), 0,
 			   (hipStream_t)stream, *r);
-	return bpr_err("k_bpr_plan");
+	return bk_err("k_bpr_plan");
 }
 
 extern "C" int sgpu_bplan_rtcp_finish(const struct sgpu_bplan_rtcp *r,
@@ -535,9 +404,7 @@ extern "C" int sgpu_bplan_rtcp_finish(const struct sgpu_bplan_rtcp *r,
 {
 	if (bpr_check(r))
 		return EINVAL;
-	const uint32_t g = (r->in.n + BPB * SGPU_BP_PPT - 1) /
-			   (BPB * SGPU_BP_PPT);
-	hipLaunchKernelGGL(k_bpr_finish, dim3(r->nb + g), dim3(BPB), 0,
-			   (hipStream_t)stream, *r);
-	return bpr_err("k_bpr_finish");
+	hipLaunchKernelGGL(k_bpr_finish, dim3(r->nb + bk_grid(r->in.n)),
+			   dim3(BPB), 0, (hipStream_t)stream, *r);
+	return bk_err("k_bpr_finish");
 }

@@ -42,69 +42,14 @@
  * reads the one record it needs) and only the tables' SSRCs are held for the
  * slot search: 158 KiB.
  *
- * No workgroup waits for another.
+ * No workgroup waits for another.  The front, both passes' look back and slot,
+ * the workgroup's segmented scan and the finish tail are
+ * plan_bucket_common.h's, with the barriers each of them contains.
  */
-#include <hip/hip_runtime.h>
-#include <errno.h>
-#include <stdio.h>
-#include "../srtpgpu.h"
-#include "plan_rtcp_seg_rx.h"
+#include "plan_bucket_common.h"
 
-#define BPB SGPU_BP_BLOCK
-#define BPRX_EPT (SGPU_BP_CAPMAX / BPB) /* entries per thread, at most */
-
-static_assert(sizeof(struct rseg_rec) == 16 &&
-	      sizeof(struct sgpu_rtcp_rec) == 16 &&
-	      offsetof(struct sgpu_rtcp_rec, blo) ==
-	      offsetof(struct rseg_rec, blo),
-	      "a stream record moves as one 16-byte word");
 static_assert(RSEG_MAX == 8, "sinfo holds 8 touched bits, ps 3 slot bits");
 static_assert(SGPU_BP_NSB <= 256, "ps holds 8 session bits");
-
-__device__ __forceinline__ struct rseg_rec bprx_ld(const struct sgpu_rtcp_rec *p)
-{
-	const uint4 a = *(const uint4 *)p;
-	struct rseg_rec r;
-	r.ssrc = a.x; r.ix = a.y; r.blo = a.z; r.bhi = a.w;
-	return r;
-}
-
-__device__ __forceinline__ struct rx_seg bprx_shfl_up(struct rx_seg v, int d)
-{
-	struct rx_seg r;
-	r.a.s = __shfl_up((long long)v.a.s, d);
-	r.a.m = __shfl_up((long long)v.a.m, d);
-	r.head = (uint32_t)__shfl_up((int)v.head, d);
-	return r;
-}
-
-/* exclusive segmented scan of one element per thread over the workgroup
- * (every thread calls it): in the wave by shuffles, across the 16 waves
- * through their aggregates (as plan_buckets_rtp_streams_rx.hip
- * bsr_excl_scan) */
-__device__ __forceinline__ struct rx_seg bprx_excl_scan(struct rx_seg v,
-							struct rx_seg *wagg)
-{
-	const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-	struct rx_seg x = v;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const struct rx_seg y = bprx_shfl_up(x, d);
-		if (lane >= (uint32_t)d)
-			x = rx_seg_combine(y, x);
-	}
-	if (lane == 63)
-		wagg[wv] = x;
-	struct rx_seg below = bprx_shfl_up(x, 1);
-	if (lane == 0)
-		below = rx_seg_identity();
-	__syncthreads();
-	struct rx_seg pre = rx_seg_identity();
-	for (uint32_t q = 0; q < wv; q++)
-		pre = rx_seg_combine(pre, wagg[q]);
-	__syncthreads();
-	return rx_seg_combine(pre, below);
-}
 
 /* ---- per bucket, the plan --------------------------------------------- */
 
@@ -163,7 +108,7 @@ bprx_rec(const struct sgpu_bplan_rtcp &P, const BprxLds &S, uint32_t l,
 	 uint32_t x)
 {
 	if (x < S.nk[l])
-		return bprx_ld(P.recs + S.t0[l] + x);
+		return bk_ld(P.recs + S.t0[l] + x);
 	return rsrx_new(S.tss[l][x]);
 }
 
@@ -185,166 +130,66 @@ k_bprx_plan(const struct sgpu_bplan_rtcp_rx R)
 	const uint32_t s0 = b << P.bshift;
 	const uint32_t ns = min(1u << P.bshift, P.nsess - s0);
 	const uint32_t EPT = P.cap / BPB;
-	uint32_t m = P.bcount[b];
-	uint32_t f = 0;
-	{
-		/* the scatter workgroups' fail words, spread over the buckets
-		 * (no workgroup waits for another) */
-		const uint32_t na = (in.n + BPB * SGPU_BP_PPT - 1) /
-				    (BPB * SGPU_BP_PPT);
-		for (uint32_t k = b + tid * P.nb; k < na; k += BPB * P.nb)
-			f |= P.afail[k];
-	}
-	if (m > P.cap) {
-		f |= SPF_SEG;           /* (the scatter flagged it too) */
-		m = 0;
-	}
 	/* the bucket's entries: packet index, session in bucket | parsed << 8 |
 	 * L << 16, SSRC, E || index */
-	uint4 ev4[BPRX_EPT];
-#pragma unroll
-	for (int j = 0; j < BPRX_EPT; j++) {
-		const uint32_t k = tid + j * BPB;
-		ev4[j] = k < m ? P.tmp[(size_t)b * P.cap + k]
-			       : make_uint4(0, 0, 0, 0);
-	}
+	uint4 ev4[BK_EPT];
+	uint32_t m;
+	uint32_t f = bk_entries(P.afail, in.n, P.nb, P.bcount, P.tmp, P.cap, &m,
+				ev4);
 	if (tid == 0) {
 		S.bf = 0;
 		S.nlate = S.ndup = 0;
 	}
-	if (tid < ns) {
-		const uint32_t s = s0 + tid;
-		const uint32_t t0 = P.toff[s], t1 = P.toff[s + 1];
-		uint32_t nk = t1 - t0;
-		if (t1 < t0 || nk > RSEG_MAX) {
-			f |= SPF_BAD;   /* (the host builds toff: never) */
-			nk = 0;
-		}
-		S.t0[tid] = t0;
-		S.nk[tid] = nk;
-		S.nst[tid] = nk;
-		S.cnt[tid] = 0;
-		S.tmask[tid] = 0;
-	}
-	for (uint32_t q = tid; q < SGPU_BP_NSB * RSEG_MAX; q += BPB) {
-		(&S.acc[0][0])[q] = 0;
-		(&S.wlo[0][0])[q] = 0;
-		(&S.whi[0][0])[q] = 0;
-	}
+	f |= bk_tables(P.toff, s0, ns, S.t0, S.nk, S.nst, S.cnt, S.tmask,
+		       &S.acc[0][0], &S.wlo[0][0], &S.whi[0][0]);
 	__syncthreads();
 	/* the tables' SSRCs, one per thread */
 	for (uint32_t q = tid; q < ns * RSEG_MAX; q += BPB) {
 		const uint32_t l = q / RSEG_MAX, x = q % RSEG_MAX;
 		S.tss[l][x] = x < S.nk[l] ? P.recs[S.t0[l] + x].ssrc : 0u;
 	}
-	/* rank in session (unstable) */
-	uint32_t ru[BPRX_EPT];
-#pragma unroll
-	for (int j = 0; j < BPRX_EPT; j++) {
-		const uint32_t k = tid + j * BPB;
-		ru[j] = 0;
-		if (k < m)
-			ru[j] = atomicAdd(&S.cnt[ev4[j].y & 0xffu], 1u);
-	}
-	__syncthreads();
-	/* segment starts (sessions, <= 256: wave 0) */
-	if (tid < 64) {
-		uint32_t c4[4], v = 0;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			c4[q] = l < ns ? S.cnt[l] : 0u;
-			v += c4[q];
-		}
-		uint32_t x = v;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t y = (uint32_t)__shfl_up((int)x, d);
-			if (tid >= (uint32_t)d)
-				x += y;
-		}
-		uint32_t run = x - v;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			if (l < SGPU_BP_NSB)
-				S.start[l] = run;
-			run += c4[q];
-		}
-	}
-	if (tid < ns && S.cnt[tid] > SGPU_BP_SEGMAX)
-		f |= SPF_SEG;
-	if (f)
-		atomicOr(&S.bf, f);
+	/* by (session, packet index): the order the reference receives them in */
+	uint32_t pos[BK_EPT];
+	bool dead = bk_sort(ev4, 0, m, ns, f, S.cnt, S.start, S.pi, &S.bf, pos);
 	f = 0;
-	__syncthreads();
-	bool dead = S.bf != 0;          /* the plan fails: nothing more */
-	if (!dead) {
-		/* grouped by session */
 #pragma unroll
-		for (int j = 0; j < BPRX_EPT; j++) {
-			const uint32_t k = tid + j * BPB;
-			if (k < m)
-				S.pi[S.start[ev4[j].y & 0xffu] + ru[j]] = ev4[j].x;
-		}
-	}
-	__syncthreads();
-	if (!dead) {
-		/* inside a session by packet index: the order the reference
-		 * receives them in */
-#pragma unroll
-		for (int j = 0; j < BPRX_EPT; j++) {
-			const uint32_t k = tid + j * BPB;
-			if (k >= m)
-				continue;
-			const uint32_t l = ev4[j].y & 0xffu;
-			const uint32_t f0 = S.start[l], c = S.cnt[l];
-			uint32_t r = 0;
-			for (uint32_t t = f0; t < f0 + c; t++)
-				r += S.pi[t] < ev4[j].x ? 1u : 0u;
-			S.v.a.idx[f0 + r] = ev4[j].x;
-			S.v.a.meta[f0 + r] = ev4[j].y;
-			S.v.a.ssrc[f0 + r] = ev4[j].z;
-			S.v.a.word[f0 + r] = ev4[j].w;
-		}
+	for (int j = 0; j < BK_EPT; j++) {
+		if (dead || tid + j * BPB >= m)
+			continue;
+		S.v.a.idx[pos[j]] = ev4[j].x;
+		S.v.a.meta[pos[j]] = ev4[j].y;
+		S.v.a.ssrc[pos[j]] = ev4[j].z;
+		S.v.a.word[pos[j]] = ev4[j].w;
 	}
 	__syncthreads();
 	/* pass 1, per sorted position: the known slot, the look back */
-	uint32_t kn[BPRX_EPT], rank[BPRX_EPT], firstk[BPRX_EPT];
+	uint32_t kn[BK_EPT], rank[BK_EPT], firstk[BK_EPT];
 #pragma unroll
-	for (int j = 0; j < BPRX_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		kn[j] = RSEG_NONE;
 		rank[j] = 0;
 		firstk[j] = k;
 		if (dead || k >= m)
 			continue;
-		const uint32_t l = S.v.a.meta[k] & 0xffu, x = S.v.a.ssrc[k];
-		struct rseg_look lk = rseg_look_init(k);
-		kn[j] = rsrx_known(S.tss[l], S.nk[l], x);
-		for (uint32_t t = S.start[l]; t < k; t++)
-			lk = rseg_look_step(lk, t, S.v.a.ssrc[t] == x);
-		S.opens[k] = (uint8_t)rseg_opens(kn[j], lk);
-		rank[j] = lk.rank;
-		firstk[j] = lk.first;
+		const uint32_t l = S.v.a.meta[k] & 0xffu;
+		kn[j] = bk_look(k, S.start[l], S.v.a.ssrc, S.tss[l], S.nk[l],
+				S.opens, &rank[j], &firstk[j]);
 	}
 	__syncthreads();
 	/* pass 2: the slot; a new stream's SSRC; the stream's arrivals; what
 	 * the packet is, into registers */
-	uint32_t sl[BPRX_EPT], pidx[BPRX_EPT], pword[BPRX_EPT], pmeta[BPRX_EPT];
+	uint32_t sl[BK_EPT], pidx[BK_EPT], pword[BK_EPT], pmeta[BK_EPT];
 #pragma unroll
-	for (int j = 0; j < BPRX_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		sl[j] = RSEG_NONE;
 		pidx[j] = pword[j] = pmeta[j] = 0;
 		if (dead || k >= m)
 			continue;
 		const uint32_t mt = S.v.a.meta[k], l = mt & 0xffu;
-		uint32_t nnew = 0;
-		if (kn[j] == RSEG_NONE)
-			for (uint32_t t = S.start[l]; t < firstk[j]; t++)
-				nnew += S.opens[t];
-		const uint32_t slot = rseg_slot(kn[j], S.nk[l], nnew);
+		const uint32_t slot = bk_slot(kn[j], firstk[j], S.start[l], S.nk[l],
+					      S.opens);
 		if (rseg_enosr(slot)) {
 			f |= SPF_SSRC;  /* a 9th stream: ENOSR on the host */
 			continue;
@@ -353,12 +198,10 @@ k_bprx_plan(const struct sgpu_bplan_rtcp_rx R)
 		pidx[j] = S.v.a.idx[k];
 		pword[j] = S.v.a.word[k];
 		pmeta[j] = mt;
-		if (S.opens[k]) {
+		if (S.opens[k])
 			S.tss[l][slot] = S.v.a.ssrc[k];
-			atomicMax(&S.nst[l], slot + 1u);
-		}
-		atomicOr(&S.tmask[l], 1u << slot);
-		atomicMax(&S.acc[l][slot], rank[j] + 1u);
+		bk_touch(l, slot, S.opens[k], rank[j] + 1u, S.nst, S.tmask,
+			 &S.acc[l][slot]);
 	}
 	if (f)
 		atomicOr(&S.bf, f);
@@ -374,7 +217,7 @@ k_bprx_plan(const struct sgpu_bplan_rtcp_rx R)
 	__syncthreads();
 	if (!dead) {
 #pragma unroll
-		for (int j = 0; j < BPRX_EPT; j++) {
+		for (int j = 0; j < BK_EPT; j++) {
 			const uint32_t k = tid + j * BPB;
 			if (k >= m || sl[j] == RSEG_NONE)
 				continue;
@@ -392,11 +235,11 @@ k_bprx_plan(const struct sgpu_bplan_rtcp_rx R)
 	 * consecutive positions per thread, the threads' aggregates scanned
 	 * across the workgroup (the sorted arrays are dead: every thread passed
 	 * the barriers behind pass 2) */
-	int64_t dv[BPRX_EPT];
+	int64_t dv[BK_EPT];
 	uint32_t hbits = 0;
 	struct rx_seg agg = rx_seg_identity();
 #pragma unroll
-	for (int j = 0; j < BPRX_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t p = tid * EPT + j;
 		dv[j] = 0;
 		if (dead || (uint32_t)j >= EPT || p >= m)
@@ -408,9 +251,9 @@ k_bprx_plan(const struct sgpu_bplan_rtcp_rx R)
 		agg = rx_seg_combine(agg, rx_seg_elem(dv[j], head));
 	}
 	{
-		struct rx_seg run = bprx_excl_scan(agg, S.wagg);
+		struct rx_seg run = bk_excl_scan(agg, S.wagg);
 #pragma unroll
-		for (int j = 0; j < BPRX_EPT; j++) {
+		for (int j = 0; j < BK_EPT; j++) {
 			const uint32_t p = tid * EPT + j;
 			if (dead || (uint32_t)j >= EPT || p >= m)
 				continue;
@@ -537,32 +380,14 @@ k_bprx_finish(const struct sgpu_bplan_rtcp_rx R)
 	 * plan out, all of it to the pinned mirror with vector stores
 	 * (out->fail is final: the plan kernel completed before the crypto
 	 * launch) */
-	if (tid < 2)
-		tot[tid] = 0;
-	__syncthreads();
-	{
-		uint32_t a = 0, d = 0;
-		for (uint32_t q = tid; q < P.nb; q += BPB) {
-			a += R.cnt[2 * q];
-			d += R.cnt[2 * q + 1];
-		}
-		if (a)
-			atomicAdd(&tot[0], a);
-		if (d)
-			atomicAdd(&tot[1], d);
-	}
-	__syncthreads();
+	bk_counts(R.cnt, P.nb, tot);
 	if (tid == 0) {
 		R.ro->nlate = tot[0];
 		R.ro->ndup = tot[1];
 		P.out->nfail = nf;
 	}
 	__syncthreads();
-	if (P.outh) {
-		const uint32_t *src = (const uint32_t *)P.out;
-		for (uint32_t w = tid; w < P.outbytes / 4u; w += BPB)
-			P.outh[w] = src[w];
-	}
+	bk_post(P.out, P.outh, P.outbytes, BK_NOWORD, 0);
 }
 
 /* ---- host side ------------------------------------------------------ */
@@ -571,11 +396,7 @@ static int bprx_check(const struct sgpu_bplan_rtcp_rx *x)
 {
 	const struct sgpu_bplan_rtcp *r = &x->r;
 	const uintptr_t o = (uintptr_t)r->out, q = (uintptr_t)x->ro;
-	if (!r->in.n || r->in.n > SGPU_BP_NMAX || r->nsess < 2 || !r->nb ||
-	    r->nb > SGPU_BP_NBMAX || r->bshift > 8 || !r->cap ||
-	    r->cap > SGPU_BP_CAPMAX || r->cap % BPB ||
-	    ((uint64_t)r->nb << r->bshift) < r->nsess ||
-	    ((uint64_t)(r->nb - 1) << r->bshift) >= r->nsess ||
+	if (bk_geom_bad(r->in.n, r->nsess, r->nb, r->bshift, r->cap) ||
 	    r->in.prot || r->in.gcm || !r->in.hmac ||
 	    !r->pos || !r->end || !r->sess || !r->endw || !r->err || !r->es ||
 	    !r->hdr || !r->desc || !r->tmp || !r->bcount || !r->afail ||
@@ -586,15 +407,6 @@ static int bprx_check(const struct sgpu_bplan_rtcp_rx *x)
 	return 0;
 }
 
-static int bprx_err(const char *what)
-{
-	const hipError_t e = hipGetLastError();
-	if (e == hipSuccess)
-		return 0;
-	fprintf(stderr, "re_srtp: %s launch: %s\n", what, hipGetErrorString(e));
-	return EIO;
-}
-
 extern "C" int sgpu_bplan_rtcp_rx_plan(const struct sgpu_bplan_rtcp_rx *r,
 				       void *stream)
 {
@@ -602,7 +414,7 @@ extern "C" int sgpu_bplan_rtcp_rx_plan(const struct sgpu_bplan_rtcp_rx *r,
 		return EINVAL;
 	hipLaunchKernelGGL(k_bprx_plan, dim3(r->r.nb), dim3(BPB), 0,
 			   (hipStream_t)stream, *r);
-	return bprx_err("k_bprx_plan");
+	return bk_err("k_bprx_plan");
 }
 
 extern "C" int sgpu_bplan_rtcp_rx_finish(const struct sgpu_bplan_rtcp_rx *r,
@@ -610,9 +422,7 @@ extern "C" int sgpu_bplan_rtcp_rx_finish(const struct sgpu_bplan_rtcp_rx *r,
 {
 	if (bprx_check(r))
 		return EINVAL;
-	const uint32_t g = (r->r.in.n + BPB * SGPU_BP_PPT - 1) /
-			   (BPB * SGPU_BP_PPT);
-	hipLaunchKernelGGL(k_bprx_finish, dim3(r->r.nb + g), dim3(BPB), 0,
-			   (hipStream_t)stream, *r);
-	return bprx_err("k_bprx_finish");
+	hipLaunchKernelGGL(k_bprx_finish, dim3(r->r.nb + bk_grid(r->r.in.n)),
+			   dim3(BPB), 0, (hipStream_t)stream, *r);
+	return bk_err("k_bprx_finish");
 }

@@ -34,41 +34,13 @@
  *                 plan out to its pinned mirror
  *
  * No workgroup waits for another.  Any failed check rejects the whole plan:
- * nothing of the caller's is modified and the host plans.
+ * nothing of the caller's is modified and the host plans.  k_bps_plan's front
+ * (entries, table words, grouping and rank), pass 2's slot and the finish tail
+ * are plan_bucket_common.h's; pass 1's step carries the seq and is its own.
  */
-#include <hip/hip_runtime.h>
-#include <errno.h>
-#include <stdio.h>
-#include "../srtpgpu.h"
-#include "plan_rtp_seg.h"
+#include "plan_bucket_common.h"
 
-#define BPB SGPU_BP_BLOCK
-#define BP_IMASK 0x3ffffffu     /* entry: packet index | length bin << 26 */
-#define BP_OBINS 64
-#define BPS_EPT (SGPU_BP_CAPMAX / BPB)  /* entries per thread, at most */
-
-static_assert(sizeof(struct tseg_rec) == 32 &&
-	      sizeof(struct sgpu_rtp_rec) == 32 &&
-	      offsetof(struct sgpu_rtp_rec, llo) ==
-	      offsetof(struct tseg_rec, llo),
-	      "a stream record moves as two 16-byte words");
 static_assert(RSEG_MAX == 8, "sinfo holds 8 touched bits");
-
-__device__ __forceinline__ struct tseg_rec bps_ld(const struct sgpu_rtp_rec *p)
-{
-	const uint4 a = ((const uint4 *)p)[0], b = ((const uint4 *)p)[1];
-	struct tseg_rec r;
-	r.ssrc = a.x; r.roc = a.y; r.sl = a.z; r.pad = 0;
-	r.llo = b.x; r.lhi = b.y; r.blo = b.z; r.bhi = b.w;
-	return r;
-}
-
-__device__ __forceinline__ void bps_st(struct sgpu_rtp_rec *p,
-				       const struct tseg_rec &r)
-{
-	((uint4 *)p)[0] = make_uint4(r.ssrc, r.roc, r.sl, 0u);
-	((uint4 *)p)[1] = make_uint4(r.llo, r.lhi, r.blo, r.bhi);
-}
 
 /* ---- per bucket, the plan --------------------------------------------- */
 
@@ -76,7 +48,7 @@ __device__ __forceinline__ void bps_st(struct sgpu_rtp_rec *p,
  * The bucket in LDS (157 KiB of the CU's 160).  The entries are written
  * once in (session, packet index) order, so a look back reads consecutive
  * words, every lane of a session the same ones; a thread keeps what it
- * learnt about its own (at most BPS_EPT) positions in registers between the
+ * learnt about its own (at most BK_EPT) positions in registers between the
  * passes.  The windows' tops take the place of the grouping's scratch, which
  * is dead once the entries are ranked.
  */
@@ -115,137 +87,48 @@ k_bps_plan(const struct sgpu_bplan_rtps R)
 	const uint32_t tid = threadIdx.x, b = blockIdx.x;
 	const uint32_t s0 = b << P.bshift;
 	const uint32_t ns = min(1u << P.bshift, P.nsess - s0);
-	uint32_t m = P.bcount[b];
-	uint32_t f = 0;
-	{
-		/* the scatter workgroups' fail words, spread over the buckets
-		 * (no workgroup waits for another) */
-		const uint32_t na = (P.n + BPB * SGPU_BP_PPT - 1) /
-				    (BPB * SGPU_BP_PPT);
-		for (uint32_t k = b + tid * P.nb; k < na; k += BPB * P.nb)
-			f |= P.afail[k];
-	}
-	if (m > P.cap) {
-		f |= SPF_SEG;           /* (the scatter flagged it too) */
-		m = 0;
-	}
 	/* the bucket's entries: index | length bin << 26, seq | session in
 	 * bucket << 16, SSRC, (place in the bin: not used) */
-	uint4 ev4[BPS_EPT];
+	uint4 ev4[BK_EPT];
+	uint32_t m;
+	uint32_t f = bk_entries(P.afail, P.n, P.nb, P.bcount, P.tmp, P.cap, &m,
+				ev4);
 #pragma unroll
-	for (int j = 0; j < BPS_EPT; j++) {
-		const uint32_t k = tid + j * BPB;
-		ev4[j] = k < m ? P.tmp[(size_t)b * P.cap + k]
-			       : make_uint4(0, 0, 0, 0);
+	for (int j = 0; j < BK_EPT; j++)
 		ev4[j].x &= BP_IMASK;
-	}
 	if (tid == 0)
 		S.bf = 0;
-	if (tid < ns) {
-		const uint32_t s = s0 + tid;
-		const uint32_t t0 = R.toff[s], t1 = R.toff[s + 1];
-		uint32_t nk = t1 - t0;
-		if (t1 < t0 || nk > RSEG_MAX) {
-			f |= SPF_BAD;   /* (the host builds toff: never) */
-			nk = 0;
-		}
-		S.nk[tid] = nk;
-		S.nst[tid] = nk;
-		S.cnt[tid] = 0;
-		S.tmask[tid] = 0;
-	}
-	for (uint32_t q = tid; q < SGPU_BP_NSB * RSEG_MAX; q += BPB) {
-		(&S.acc[0][0])[q] = 0;
-		(&S.wlo[0][0])[q] = 0;
-		(&S.whi[0][0])[q] = 0;
-	}
+	f |= bk_tables(R.toff, s0, ns, NULL, S.nk, S.nst, S.cnt, S.tmask,
+		       &S.acc[0][0], &S.wlo[0][0], &S.whi[0][0]);
 	__syncthreads();
 	/* the sessions' tables, one record per thread */
 	for (uint32_t q = tid; q < ns * RSEG_MAX; q += BPB) {
 		const uint32_t l = q / RSEG_MAX, x = q % RSEG_MAX;
 		struct tseg_rec r = {0, 0, 0, 0, 0, 0, 0, 0};
 		if (x < S.nk[l])
-			r = bps_ld(R.recs + R.toff[s0 + l] + x);
+			r = bk_ld(R.recs + R.toff[s0 + l] + x);
 		S.rec[l][x] = r;
 	}
-	/* rank in session (unstable) */
-	uint32_t ru[BPS_EPT];
-#pragma unroll
-	for (int j = 0; j < BPS_EPT; j++) {
-		const uint32_t k = tid + j * BPB;
-		ru[j] = 0;
-		if (k < m)
-			ru[j] = atomicAdd(&S.cnt[ev4[j].y >> 16 & 0xffu], 1u);
-	}
-	__syncthreads();
-	/* segment starts (sessions, <= 256: wave 0) */
-	if (tid < 64) {
-		uint32_t c4[4], v = 0;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			c4[q] = l < ns ? S.cnt[l] : 0u;
-			v += c4[q];
-		}
-		uint32_t x = v;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t y = (uint32_t)__shfl_up((int)x, d);
-			if (tid >= (uint32_t)d)
-				x += y;
-		}
-		uint32_t run = x - v;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			if (l < SGPU_BP_NSB)
-				S.start[l] = run;
-			run += c4[q];
-		}
-	}
-	if (tid < ns && S.cnt[tid] > SGPU_BP_SEGMAX)
-		f |= SPF_SEG;
-	if (f)
-		atomicOr(&S.bf, f);
+	/* by (session, packet index): the order the reference sees them in */
+	uint32_t pos[BK_EPT];
+	const bool dead = bk_sort(ev4, 16, m, ns, f, S.cnt, S.start, S.u.gidx,
+				  &S.bf, pos);
 	f = 0;
-	__syncthreads();
-	const bool dead = S.bf != 0;    /* the plan fails: nothing more */
-	if (!dead) {
-		/* grouped by session */
 #pragma unroll
-		for (int j = 0; j < BPS_EPT; j++) {
-			const uint32_t k = tid + j * BPB;
-			if (k < m)
-				S.u.gidx[S.start[ev4[j].y >> 16 & 0xffu] + ru[j]] =
-					ev4[j].x;
-		}
-	}
-	__syncthreads();
-	if (!dead) {
-		/* inside a session by packet index: the order the reference
-		 * sees them in */
-#pragma unroll
-		for (int j = 0; j < BPS_EPT; j++) {
-			const uint32_t k = tid + j * BPB;
-			if (k >= m)
-				continue;
-			const uint32_t l = ev4[j].y >> 16 & 0xffu;
-			const uint32_t f0 = S.start[l], c = S.cnt[l];
-			uint32_t r = 0;
-			for (uint32_t t = f0; t < f0 + c; t++)
-				r += S.u.gidx[t] < ev4[j].x ? 1u : 0u;
-			S.idx[f0 + r] = ev4[j].x;
-			S.sq[f0 + r] = (uint16_t)ev4[j].y;
-			S.sl[f0 + r] = (uint8_t)l;
-			S.ssrc[f0 + r] = ev4[j].z;
-		}
+	for (int j = 0; j < BK_EPT; j++) {
+		if (dead || tid + j * BPB >= m)
+			continue;
+		S.idx[pos[j]] = ev4[j].x;
+		S.sq[pos[j]] = (uint16_t)ev4[j].y;
+		S.sl[pos[j]] = (uint8_t)bk_key(ev4[j], 16);
+		S.ssrc[pos[j]] = ev4[j].z;
 	}
 	__syncthreads();
 	/* pass 1, per sorted position: the known slot, the look back */
-	uint32_t kn[BPS_EPT];
-	struct tseg_look lk[BPS_EPT];
+	uint32_t kn[BK_EPT];
+	struct tseg_look lk[BK_EPT];
 #pragma unroll
-	for (int j = 0; j < BPS_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		kn[j] = RSEG_NONE;
 		lk[j] = tseg_look_init(k);
@@ -263,19 +146,16 @@ k_bps_plan(const struct sgpu_bplan_rtps R)
 	}
 	__syncthreads();
 	/* pass 2: the slot; a new stream's record; the stream's packet count */
-	uint32_t sl[BPS_EPT];
+	uint32_t sl[BK_EPT];
 #pragma unroll
-	for (int j = 0; j < BPS_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		sl[j] = RSEG_NONE;
 		if (dead || k >= m)
 			continue;
 		const uint32_t l = S.sl[k];
-		uint32_t nnew = 0;
-		if (kn[j] == RSEG_NONE)
-			for (uint32_t t = S.start[l]; t < lk[j].a.first; t++)
-				nnew += S.opens[t];
-		const uint32_t slot = rseg_slot(kn[j], S.nk[l], nnew);
+		const uint32_t slot = bk_slot(kn[j], lk[j].a.first, S.start[l],
+					      S.nk[l], S.opens);
 		if (rseg_enosr(slot)) {
 			f |= SPF_SSRC;  /* a 9th stream: ENOSR on the host */
 			continue;
@@ -284,18 +164,17 @@ k_bps_plan(const struct sgpu_bplan_rtps R)
 		if (S.opens[k]) {
 			const struct tseg_rec r = {S.ssrc[k], 0, 0, 0, 0, 0, 0, 0};
 			S.rec[l][slot] = r;
-			atomicMax(&S.nst[l], slot + 1u);
 		}
-		atomicOr(&S.tmask[l], 1u << slot);
-		atomicMax(&S.acc[l][slot], lk[j].a.rank + 1u);
+		bk_touch(l, slot, S.opens[k], lk[j].a.rank + 1u, S.nst, S.tmask,
+			 &S.acc[l][slot]);
 	}
 	__syncthreads();
 	/* pass 3: the rule, desc; the stream's last packet: its window's top
 	 * (u.gidx is dead: every thread passed the barriers behind the rank) */
-	struct tseg_pkt pk[BPS_EPT];
+	struct tseg_pkt pk[BK_EPT];
 	uint32_t lastm = 0;
 #pragma unroll
-	for (int j = 0; j < BPS_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		if (dead || k >= m || sl[j] == RSEG_NONE)
 			continue;
@@ -315,7 +194,7 @@ k_bps_plan(const struct sgpu_bplan_rtps R)
 	/* pass 4 (unprotect): one window bit per packet within 64 of the top */
 	if (!prot) {
 #pragma unroll
-		for (int j = 0; j < BPS_EPT; j++) {
+		for (int j = 0; j < BK_EPT; j++) {
 			const uint32_t k = tid + j * BPB;
 			if (dead || k >= m || sl[j] == RSEG_NONE)
 				continue;
@@ -333,20 +212,20 @@ k_bps_plan(const struct sgpu_bplan_rtps R)
 	 * its last packet, the others as they were */
 	if (held) {
 #pragma unroll
-		for (int j = 0; j < BPS_EPT; j++) {
+		for (int j = 0; j < BK_EPT; j++) {
 			if (!(lastm >> j & 1u))
 				continue;
 			const uint32_t k = tid + j * BPB, l = S.sl[k];
 			const uint64_t bits = (uint64_t)S.whi[l][sl[j]] << 32 |
 					      S.wlo[l][sl[j]];
-			bps_st(R.sout + (size_t)(s0 + l) * RSEG_MAX + sl[j],
+			bk_st(R.sout + (size_t)(s0 + l) * RSEG_MAX + sl[j],
 			       tseg_after(prot, S.rec[l][sl[j]], pk[j], bits));
 		}
 		for (uint32_t q = tid; q < ns * RSEG_MAX; q += BPB) {
 			const uint32_t l = q / RSEG_MAX, x = q % RSEG_MAX;
 			if (!S.tmask[l] || x >= S.nst[l] || (S.tmask[l] >> x & 1u))
 				continue;
-			bps_st(R.sout + (size_t)(s0 + l) * RSEG_MAX + x,
+			bk_st(R.sout + (size_t)(s0 + l) * RSEG_MAX + x,
 			       S.rec[l][x]);
 		}
 	}
@@ -399,12 +278,8 @@ k_bps_finish(const struct sgpu_bplan_rtps R)
 	 * plan kernel completed before the crypto launches) */
 	if (tid == 0)
 		P.out->nfail = nf;
-	if (P.outh) {
-		const uint32_t *src = (const uint32_t *)P.out;
-		const uint32_t wn = offsetof(struct sgpu_plan_out, nfail) / 4u;
-		for (uint32_t w = tid; w < P.outbytes / 4u; w += BPB)
-			P.outh[w] = w == wn ? nf : src[w];
-	}
+	bk_post(P.out, P.outh, P.outbytes,
+		offsetof(struct sgpu_plan_out, nfail) / 4u, nf);
 }
 
 /* ---- host side ------------------------------------------------------ */
@@ -412,26 +287,13 @@ k_bps_finish(const struct sgpu_bplan_rtps R)
 static int bps_check(const struct sgpu_bplan_rtps *r)
 {
 	const struct sgpu_bplan *b = &r->b;
-	if (!b->n || b->n > SGPU_BP_NMAX || b->nsess < 2 || !b->nb ||
-	    b->nb > SGPU_BP_NBMAX || b->bshift > 8 || !b->cap ||
-	    b->cap > SGPU_BP_CAPMAX || b->cap % BPB ||
-	    ((uint64_t)b->nb << b->bshift) < b->nsess ||
-	    ((uint64_t)(b->nb - 1) << b->bshift) >= b->nsess ||
+	if (bk_geom_bad(b->n, b->nsess, b->nb, b->bshift, b->cap) ||
 	    !b->endw || !b->err || !b->es || !b->desc || !b->tmp ||
 	    !b->bcount || !b->obins || !b->afail || !b->out || !b->nfail ||
 	    !r->toff || !r->recs || !r->sout || !r->sinfo ||
 	    b->outbytes % 4u || b->outbytes > sizeof(struct sgpu_plan_out))
 		return EINVAL;
 	return 0;
-}
-
-static int bps_err(const char *what)
-{
-	const hipError_t e = hipGetLastError();
-	if (e == hipSuccess)
-		return 0;
-	fprintf(stderr, "re_srtp: %s launch: %s\n", what, hipGetErrorString(e));
-	return EIO;
 }
 
 extern "C" int sgpu_bplan_rtps_plan(const struct sgpu_bplan_rtps *r,
@@ -441,7 +303,7 @@ extern "C" int sgpu_bplan_rtps_plan(const struct sgpu_bplan_rtps *r,
 		return EINVAL;
 	hipLaunchKernelGGL(k_bps_plan, dim3(r->b.nb), dim3(BPB), 0,
 			   (hipStream_t)stream, *r);
-	return bps_err("k_bps_plan");
+	return bk_err("k_bps_plan");
 }
 
 extern "C" int sgpu_bplan_rtps_finish(const struct sgpu_bplan_rtps *r,
@@ -449,9 +311,7 @@ extern "C" int sgpu_bplan_rtps_finish(const struct sgpu_bplan_rtps *r,
 {
 	if (bps_check(r))
 		return EINVAL;
-	const uint32_t g = (r->b.n + BPB * SGPU_BP_PPT - 1) /
-			   (BPB * SGPU_BP_PPT);
-	hipLaunchKernelGGL(k_bps_finish, dim3(r->b.nb + g), dim3(BPB), 0,
-			   (hipStream_t)stream, *r);
-	return bps_err("k_bps_finish");
+	hipLaunchKernelGGL(k_bps_finish, dim3(r->b.nb + bk_grid(r->b.n)),
+			   dim3(BPB), 0, (hipStream_t)stream, *r);
+	return bk_err("k_bps_finish");
 }

@@ -40,77 +40,13 @@
  * dead once every thread holds its packets' slot and rank in registers, and
  * u[] / mx[] take their place: 138 KiB.
  *
- * No workgroup waits for another.
+ * No workgroup waits for another.  The front, both passes' look back and slot,
+ * the workgroup's segmented scan and the finish tail are
+ * plan_bucket_common.h's, with the barriers each of them contains.
  */
-#include <hip/hip_runtime.h>
-#include <errno.h>
-#include <stdio.h>
-#include "../srtpgpu.h"
-#include "plan_rtp_seg_rx.h"
+#include "plan_bucket_common.h"
 
-#define BPB SGPU_BP_BLOCK
-#define BP_IMASK 0x3ffffffu     /* entry: packet index | length bin << 26 */
-#define BP_OBINS 64
-#define BSR_EPT (SGPU_BP_CAPMAX / BPB)  /* entries per thread, at most */
-
-static_assert(sizeof(struct tseg_rec) == 32 &&
-	      sizeof(struct sgpu_rtp_rec) == 32 &&
-	      offsetof(struct sgpu_rtp_rec, llo) ==
-	      offsetof(struct tseg_rec, llo),
-	      "a stream record moves as two 16-byte words");
 static_assert(RSEG_MAX == 8, "sinfo holds 8 touched bits, ps 3 slot bits");
-
-__device__ __forceinline__ struct tseg_rec bsr_ld(const struct sgpu_rtp_rec *p)
-{
-	const uint4 a = ((const uint4 *)p)[0], b = ((const uint4 *)p)[1];
-	struct tseg_rec r;
-	r.ssrc = a.x; r.roc = a.y; r.sl = a.z; r.pad = 0;
-	r.llo = b.x; r.lhi = b.y; r.blo = b.z; r.bhi = b.w;
-	return r;
-}
-
-__device__ __forceinline__ void bsr_st(struct sgpu_rtp_rec *p,
-				       const struct tseg_rec &r)
-{
-	((uint4 *)p)[0] = make_uint4(r.ssrc, r.roc, r.sl, 0u);
-	((uint4 *)p)[1] = make_uint4(r.llo, r.lhi, r.blo, r.bhi);
-}
-
-__device__ __forceinline__ struct rx_seg bsr_shfl_up(struct rx_seg v, int d)
-{
-	struct rx_seg r;
-	r.a.s = __shfl_up((long long)v.a.s, d);
-	r.a.m = __shfl_up((long long)v.a.m, d);
-	r.head = (uint32_t)__shfl_up((int)v.head, d);
-	return r;
-}
-
-/* exclusive segmented scan of one element per thread over the workgroup
- * (every thread calls it): in the wave by shuffles, across the 16 waves
- * through their aggregates (as plan_buckets_rx.hip brx_excl_scan) */
-__device__ __forceinline__ struct rx_seg bsr_excl_scan(struct rx_seg v,
-						       struct rx_seg *wagg)
-{
-	const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-	struct rx_seg x = v;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const struct rx_seg y = bsr_shfl_up(x, d);
-		if (lane >= (uint32_t)d)
-			x = rx_seg_combine(y, x);
-	}
-	if (lane == 63)
-		wagg[wv] = x;
-	struct rx_seg below = bsr_shfl_up(x, 1);
-	if (lane == 0)
-		below = rx_seg_identity();
-	__syncthreads();
-	struct rx_seg pre = rx_seg_identity();
-	for (uint32_t q = 0; q < wv; q++)
-		pre = rx_seg_combine(pre, wagg[q]);
-	__syncthreads();
-	return rx_seg_combine(pre, below);
-}
 
 /* ---- per bucket, the plan --------------------------------------------- */
 
@@ -163,7 +99,7 @@ bsr_rec(const struct sgpu_bplan_rtps &T, const BsrLds &S, uint32_t l,
 	uint32_t x)
 {
 	if (x < S.nk[l])
-		return bsr_ld(T.recs + S.t0[l] + x);
+		return bk_ld(T.recs + S.t0[l] + x);
 	return tsrx_new(S.tss[l][x]);
 }
 
@@ -185,168 +121,70 @@ k_bsr_plan(const struct sgpu_bplan_rtps_rx R)
 	const uint32_t s0 = b << P.bshift;
 	const uint32_t ns = min(1u << P.bshift, P.nsess - s0);
 	const uint32_t EPT = P.cap / BPB;
-	uint32_t m = P.bcount[b];
-	uint32_t f = 0;
-	{
-		/* the scatter workgroups' fail words, spread over the buckets
-		 * (no workgroup waits for another) */
-		const uint32_t na = (P.n + BPB * SGPU_BP_PPT - 1) /
-				    (BPB * SGPU_BP_PPT);
-		for (uint32_t k = b + tid * P.nb; k < na; k += BPB * P.nb)
-			f |= P.afail[k];
-	}
-	if (m > P.cap) {
-		f |= SPF_SEG;           /* (the scatter flagged it too) */
-		m = 0;
-	}
 	/* the bucket's entries: index | length bin << 26, seq | session in
 	 * bucket << 16, SSRC, (place in the bin: not used) */
-	uint4 ev4[BSR_EPT];
+	uint4 ev4[BK_EPT];
+	uint32_t m;
+	uint32_t f = bk_entries(P.afail, P.n, P.nb, P.bcount, P.tmp, P.cap, &m,
+				ev4);
 #pragma unroll
-	for (int j = 0; j < BSR_EPT; j++) {
-		const uint32_t k = tid + j * BPB;
-		ev4[j] = k < m ? P.tmp[(size_t)b * P.cap + k]
-			       : make_uint4(0, 0, 0, 0);
+	for (int j = 0; j < BK_EPT; j++)
 		ev4[j].x &= BP_IMASK;
-	}
 	if (tid == 0) {
 		S.bf = 0;
 		S.nlate = S.ndup = 0;
 	}
-	if (tid < ns) {
-		const uint32_t s = s0 + tid;
-		const uint32_t t0 = T.toff[s], t1 = T.toff[s + 1];
-		uint32_t nk = t1 - t0;
-		if (t1 < t0 || nk > RSEG_MAX) {
-			f |= SPF_BAD;   /* (the host builds toff: never) */
-			nk = 0;
-		}
-		S.t0[tid] = t0;
-		S.nk[tid] = nk;
-		S.nst[tid] = nk;
-		S.cnt[tid] = 0;
-		S.tmask[tid] = 0;
-	}
-	for (uint32_t q = tid; q < SGPU_BP_NSB * RSEG_MAX; q += BPB) {
-		(&S.acc[0][0])[q] = 0;
-		(&S.wlo[0][0])[q] = 0;
-		(&S.whi[0][0])[q] = 0;
-	}
+	f |= bk_tables(T.toff, s0, ns, S.t0, S.nk, S.nst, S.cnt, S.tmask,
+		       &S.acc[0][0], &S.wlo[0][0], &S.whi[0][0]);
 	__syncthreads();
 	/* the tables' SSRCs, one per thread */
 	for (uint32_t q = tid; q < ns * RSEG_MAX; q += BPB) {
 		const uint32_t l = q / RSEG_MAX, x = q % RSEG_MAX;
 		S.tss[l][x] = x < S.nk[l] ? T.recs[S.t0[l] + x].ssrc : 0u;
 	}
-	/* rank in session (unstable) */
-	uint32_t ru[BSR_EPT];
-#pragma unroll
-	for (int j = 0; j < BSR_EPT; j++) {
-		const uint32_t k = tid + j * BPB;
-		ru[j] = 0;
-		if (k < m)
-			ru[j] = atomicAdd(&S.cnt[ev4[j].y >> 16 & 0xffu], 1u);
-	}
-	__syncthreads();
-	/* segment starts (sessions, <= 256: wave 0) */
-	if (tid < 64) {
-		uint32_t c4[4], v = 0;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			c4[q] = l < ns ? S.cnt[l] : 0u;
-			v += c4[q];
-		}
-		uint32_t x = v;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t y = (uint32_t)__shfl_up((int)x, d);
-			if (tid >= (uint32_t)d)
-				x += y;
-		}
-		uint32_t run = x - v;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			if (l < SGPU_BP_NSB)
-				S.start[l] = run;
-			run += c4[q];
-		}
-	}
-	if (tid < ns && S.cnt[tid] > SGPU_BP_SEGMAX)
-		f |= SPF_SEG;
-	if (f)
-		atomicOr(&S.bf, f);
+	/* by (session, packet index): the order the reference receives them in */
+	uint32_t pos[BK_EPT];
+	bool dead = bk_sort(ev4, 16, m, ns, f, S.cnt, S.start, S.v.a.gidx, &S.bf,
+			    pos);
 	f = 0;
-	__syncthreads();
-	bool dead = S.bf != 0;          /* the plan fails: nothing more */
-	if (!dead) {
-		/* grouped by session */
 #pragma unroll
-		for (int j = 0; j < BSR_EPT; j++) {
-			const uint32_t k = tid + j * BPB;
-			if (k < m)
-				S.v.a.gidx[S.start[ev4[j].y >> 16 & 0xffu] + ru[j]] =
-					ev4[j].x;
-		}
-	}
-	__syncthreads();
-	if (!dead) {
-		/* inside a session by packet index: the order the reference
-		 * receives them in */
-#pragma unroll
-		for (int j = 0; j < BSR_EPT; j++) {
-			const uint32_t k = tid + j * BPB;
-			if (k >= m)
-				continue;
-			const uint32_t l = ev4[j].y >> 16 & 0xffu;
-			const uint32_t f0 = S.start[l], c = S.cnt[l];
-			uint32_t r = 0;
-			for (uint32_t t = f0; t < f0 + c; t++)
-				r += S.v.a.gidx[t] < ev4[j].x ? 1u : 0u;
-			S.v.a.idx[f0 + r] = ev4[j].x;
-			S.v.a.sq[f0 + r] = (uint16_t)ev4[j].y;
-			S.v.a.sl[f0 + r] = (uint8_t)l;
-			S.v.a.ssrc[f0 + r] = ev4[j].z;
-		}
+	for (int j = 0; j < BK_EPT; j++) {
+		if (dead || tid + j * BPB >= m)
+			continue;
+		S.v.a.idx[pos[j]] = ev4[j].x;
+		S.v.a.sq[pos[j]] = (uint16_t)ev4[j].y;
+		S.v.a.sl[pos[j]] = (uint8_t)bk_key(ev4[j], 16);
+		S.v.a.ssrc[pos[j]] = ev4[j].z;
 	}
 	__syncthreads();
 	/* pass 1, per sorted position: the known slot, the look back */
-	uint32_t kn[BSR_EPT], rank[BSR_EPT], firstk[BSR_EPT];
+	uint32_t kn[BK_EPT], rank[BK_EPT], firstk[BK_EPT];
 #pragma unroll
-	for (int j = 0; j < BSR_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		kn[j] = RSEG_NONE;
 		rank[j] = 0;
 		firstk[j] = k;
 		if (dead || k >= m)
 			continue;
-		const uint32_t l = S.v.a.sl[k], x = S.v.a.ssrc[k];
-		struct rseg_look lk = rseg_look_init(k);
-		kn[j] = tsrx_known(S.tss[l], S.nk[l], x);
-		for (uint32_t t = S.start[l]; t < k; t++)
-			lk = rseg_look_step(lk, t, S.v.a.ssrc[t] == x);
-		S.v.a.opens[k] = (uint8_t)rseg_opens(kn[j], lk);
-		rank[j] = lk.rank;
-		firstk[j] = lk.first;
+		const uint32_t l = S.v.a.sl[k];
+		kn[j] = bk_look(k, S.start[l], S.v.a.ssrc, S.tss[l], S.nk[l],
+				S.v.a.opens, &rank[j], &firstk[j]);
 	}
 	__syncthreads();
 	/* pass 2: the slot; a new stream's SSRC; the stream's arrivals; what
 	 * the packet is, into registers */
-	uint32_t sl[BSR_EPT], pidx[BSR_EPT], pseq[BSR_EPT], psess[BSR_EPT];
+	uint32_t sl[BK_EPT], pidx[BK_EPT], pseq[BK_EPT], psess[BK_EPT];
 #pragma unroll
-	for (int j = 0; j < BSR_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		sl[j] = RSEG_NONE;
 		pidx[j] = pseq[j] = psess[j] = 0;
 		if (dead || k >= m)
 			continue;
 		const uint32_t l = S.v.a.sl[k];
-		uint32_t nnew = 0;
-		if (kn[j] == RSEG_NONE)
-			for (uint32_t t = S.start[l]; t < firstk[j]; t++)
-				nnew += S.v.a.opens[t];
-		const uint32_t slot = rseg_slot(kn[j], S.nk[l], nnew);
+		const uint32_t slot = bk_slot(kn[j], firstk[j], S.start[l], S.nk[l],
+					      S.v.a.opens);
 		if (rseg_enosr(slot)) {
 			f |= SPF_SSRC;  /* a 9th stream: ENOSR on the host */
 			continue;
@@ -355,12 +193,10 @@ k_bsr_plan(const struct sgpu_bplan_rtps_rx R)
 		pidx[j] = S.v.a.idx[k];
 		pseq[j] = S.v.a.sq[k];
 		psess[j] = l;
-		if (S.v.a.opens[k]) {
+		if (S.v.a.opens[k])
 			S.tss[l][slot] = S.v.a.ssrc[k];
-			atomicMax(&S.nst[l], slot + 1u);
-		}
-		atomicOr(&S.tmask[l], 1u << slot);
-		atomicMax(&S.acc[l][slot], rank[j] + 1u);
+		bk_touch(l, slot, S.v.a.opens[k], rank[j] + 1u, S.nst, S.tmask,
+			 &S.acc[l][slot]);
 	}
 	if (f)
 		atomicOr(&S.bf, f);
@@ -376,7 +212,7 @@ k_bsr_plan(const struct sgpu_bplan_rtps_rx R)
 	__syncthreads();
 	if (!dead) {
 #pragma unroll
-		for (int j = 0; j < BSR_EPT; j++) {
+		for (int j = 0; j < BK_EPT; j++) {
 			const uint32_t k = tid + j * BPB;
 			if (k >= m || sl[j] == RSEG_NONE)
 				continue;
@@ -391,11 +227,11 @@ k_bsr_plan(const struct sgpu_bplan_rtps_rx R)
 	 * consecutive positions per thread, the threads' aggregates scanned
 	 * across the workgroup (the sorted arrays are dead: every thread passed
 	 * the barriers behind pass 2) */
-	int64_t dv[BSR_EPT];
+	int64_t dv[BK_EPT];
 	uint32_t hbits = 0;
 	struct rx_seg agg = rx_seg_identity();
 #pragma unroll
-	for (int j = 0; j < BSR_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t p = tid * EPT + j;
 		dv[j] = 0;
 		if (dead || (uint32_t)j >= EPT || p >= m)
@@ -417,9 +253,9 @@ k_bsr_plan(const struct sgpu_bplan_rtps_rx R)
 		agg = rx_seg_combine(agg, rx_seg_elem(dv[j], head));
 	}
 	{
-		struct rx_seg run = bsr_excl_scan(agg, S.wagg);
+		struct rx_seg run = bk_excl_scan(agg, S.wagg);
 #pragma unroll
-		for (int j = 0; j < BSR_EPT; j++) {
+		for (int j = 0; j < BK_EPT; j++) {
 			const uint32_t p = tid * EPT + j;
 			if (dead || (uint32_t)j >= EPT || p >= m)
 				continue;
@@ -490,7 +326,7 @@ k_bsr_plan(const struct sgpu_bplan_rtps_rx R)
 						(uint64_t)S.whi[l][x] << 32 |
 						S.wlo[l][x]);
 			}
-			bsr_st(T.sout + (size_t)(s0 + l) * RSEG_MAX + x, st);
+			bk_st(T.sout + (size_t)(s0 + l) * RSEG_MAX + x, st);
 		}
 	}
 	if (tid < ns)
@@ -551,32 +387,14 @@ k_bsr_finish(const struct sgpu_bplan_rtps_rx R)
 	 * plan out, all of it to the pinned mirror with vector stores
 	 * (out->fail is final: the plan kernel completed before the crypto
 	 * launches) */
-	if (tid < 2)
-		tot[tid] = 0;
-	__syncthreads();
-	{
-		uint32_t a = 0, d = 0;
-		for (uint32_t q = tid; q < P.nb; q += BPB) {
-			a += R.cnt[2 * q];
-			d += R.cnt[2 * q + 1];
-		}
-		if (a)
-			atomicAdd(&tot[0], a);
-		if (d)
-			atomicAdd(&tot[1], d);
-	}
-	__syncthreads();
+	bk_counts(R.cnt, P.nb, tot);
 	if (tid == 0) {
 		R.ro->nlate = tot[0];
 		R.ro->ndup = tot[1];
 		P.out->nfail = nf;
 	}
 	__syncthreads();
-	if (P.outh) {
-		const uint32_t *src = (const uint32_t *)P.out;
-		for (uint32_t w = tid; w < P.outbytes / 4u; w += BPB)
-			P.outh[w] = src[w];
-	}
+	bk_post(P.out, P.outh, P.outbytes, BK_NOWORD, 0);
 }
 
 /* ---- host side ------------------------------------------------------ */
@@ -584,11 +402,7 @@ k_bsr_finish(const struct sgpu_bplan_rtps_rx R)
 static int bsr_check(const struct sgpu_bplan_rtps_rx *r)
 {
 	const struct sgpu_bplan *b = &r->s.b;
-	if (!b->n || b->n > SGPU_BP_NMAX || b->nsess < 2 || !b->nb ||
-	    b->nb > SGPU_BP_NBMAX || b->bshift > 8 || !b->cap ||
-	    b->cap > SGPU_BP_CAPMAX || b->cap % BPB ||
-	    ((uint64_t)b->nb << b->bshift) < b->nsess ||
-	    ((uint64_t)(b->nb - 1) << b->bshift) >= b->nsess ||
+	if (bk_geom_bad(b->n, b->nsess, b->nb, b->bshift, b->cap) ||
 	    b->prot || !b->posw || !b->endw || !b->err || !b->es || !b->hdr ||
 	    !b->desc || !b->tmp || !b->bcount || !b->obins || !b->afail ||
 	    !b->out || !b->nfail || !r->s.toff || !r->s.recs || !r->s.sout ||
@@ -598,15 +412,6 @@ static int bsr_check(const struct sgpu_bplan_rtps_rx *r)
 	return 0;
 }
 
-static int bsr_err(const char *what)
-{
-	const hipError_t e = hipGetLastError();
-	if (e == hipSuccess)
-		return 0;
-	fprintf(stderr, "re_srtp: %s launch: %s\n", what, hipGetErrorString(e));
-	return EIO;
-}
-
 extern "C" int sgpu_bplan_rtps_rx_plan(const struct sgpu_bplan_rtps_rx *r,
 				       void *stream)
 {
@@ -614,7 +419,7 @@ extern "C" int sgpu_bplan_rtps_rx_plan(const struct sgpu_bplan_rtps_rx *r,
 		return EINVAL;
 	hipLaunchKernelGGL(k_bsr_plan, dim3(r->s.b.nb), dim3(BPB), 0,
 			   (hipStream_t)stream, *r);
-	return bsr_err("k_bsr_plan");
+	return bk_err("k_bsr_plan");
 }
 
 extern "C" int sgpu_bplan_rtps_rx_finish(const struct sgpu_bplan_rtps_rx *r,
@@ -622,9 +427,7 @@ extern "C" int sgpu_bplan_rtps_rx_finish(const struct sgpu_bplan_rtps_rx *r,
 {
 	if (bsr_check(r))
 		return EINVAL;
-	const uint32_t g = (r->s.b.n + BPB * SGPU_BP_PPT - 1) /
-			   (BPB * SGPU_BP_PPT);
-	hipLaunchKernelGGL(k_bsr_finish, dim3(r->s.b.nb + g), dim3(BPB), 0,
-			   (hipStream_t)stream, *r);
-	return bsr_err("k_bsr_finish");
+	hipLaunchKernelGGL(k_bsr_finish, dim3(r->s.b.nb + bk_grid(r->s.b.n)),
+			   dim3(BPB), 0, (hipStream_t)stream, *r);
+	return bk_err("k_bsr_finish");
 }

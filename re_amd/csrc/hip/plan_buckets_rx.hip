@@ -29,82 +29,16 @@
  *                   the resident table; always: the scatter's counters back
  *                   to zero, the call's outcome to the pinned mirror.
  *
- * No workgroup waits for another.
+ * No workgroup waits for another.  The front (entries, segment starts, the
+ * order inside a session), the workgroup's segmented scan and the finish tail
+ * are plan_bucket_common.h's.
  */
-#include <hip/hip_runtime.h>
-#include <errno.h>
-#include <stdio.h>
-#include "../srtpgpu.h"
-#include "plan_rx_rule.h"
-
-#define BPB SGPU_BP_BLOCK
-#define BP_IMASK 0x3ffffffu     /* entry: packet index | length bin << 26 */
-#define BP_OBINS 64
-#define BP_EPT (SGPU_BP_CAPMAX / BPB)   /* entries per thread, at most */
-
-static_assert(sizeof(struct sgpu_sstate) == 32 &&
-	      offsetof(struct sgpu_sstate, flags) == 12,
-	      "brx_ld/brx_st move the state as two 16-byte words");
-
-__device__ __forceinline__ struct sgpu_sstate brx_ld(const struct sgpu_sstate *p)
-{
-	const uint4 a = ((const uint4 *)p)[0], b = ((const uint4 *)p)[1];
-	struct sgpu_sstate s;
-	s.ssrc = a.x; s.roc = a.y; s.s_l = a.z; s.flags = a.w;
-	s.lix = (uint64_t)b.y << 32 | b.x;
-	s.bitmap = (uint64_t)b.w << 32 | b.z;
-	return s;
-}
-
-__device__ __forceinline__ void brx_st(struct sgpu_sstate *p,
-				       const struct sgpu_sstate &s)
-{
-	((uint4 *)p)[0] = make_uint4(s.ssrc, s.roc, s.s_l, s.flags);
-	((uint4 *)p)[1] = make_uint4((uint32_t)s.lix, (uint32_t)(s.lix >> 32),
-				     (uint32_t)s.bitmap,
-				     (uint32_t)(s.bitmap >> 32));
-}
+#include "plan_bucket_common.h"
 
 /* sgpu_desc() (srtpgpu.h) on the device */
 __device__ __forceinline__ uint64_t brx_desc(int64_t ix, uint32_t flags)
 {
 	return ((uint64_t)ix & 0xffffffffffffull) | ((uint64_t)flags << 48);
-}
-
-__device__ __forceinline__ struct rx_seg brx_shfl_up(struct rx_seg v, int d)
-{
-	struct rx_seg r;
-	r.a.s = __shfl_up((long long)v.a.s, d);
-	r.a.m = __shfl_up((long long)v.a.m, d);
-	r.head = (uint32_t)__shfl_up((int)v.head, d);
-	return r;
-}
-
-/* exclusive segmented scan of one element per thread over the workgroup
- * (every thread calls it): in the wave by shuffles, across the 16 waves
- * through their aggregates */
-__device__ __forceinline__ struct rx_seg brx_excl_scan(struct rx_seg v,
-						       struct rx_seg *wagg)
-{
-	const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-	struct rx_seg x = v;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const struct rx_seg y = brx_shfl_up(x, d);
-		if (lane >= (uint32_t)d)
-			x = rx_seg_combine(y, x);
-	}
-	if (lane == 63)
-		wagg[wv] = x;
-	struct rx_seg below = brx_shfl_up(x, 1);
-	if (lane == 0)
-		below = rx_seg_identity();
-	__syncthreads();
-	struct rx_seg pre = rx_seg_identity();
-	for (uint32_t q = 0; q < wv; q++)
-		pre = rx_seg_combine(pre, wagg[q]);
-	__syncthreads();
-	return rx_seg_combine(pre, below);
 }
 
 /*
@@ -163,29 +97,12 @@ k_bp_rx_plan(const struct sgpu_bplan_rx R)
 	const uint32_t s0 = b << P.bshift;
 	const uint32_t ns = min(1u << P.bshift, P.nsess - s0);
 	const uint32_t EPT = P.cap / BPB;
-	uint32_t m = P.bcount[b];
-	uint32_t f = 0;
-	{
-		/* the scatter workgroups' fail words, spread over the buckets
-		 * (no workgroup waits for another) */
-		const uint32_t na = (P.n + BPB * SGPU_BP_PPT - 1) /
-				    (BPB * SGPU_BP_PPT);
-		for (uint32_t k = b + tid * P.nb; k < na; k += BPB * P.nb)
-			f |= P.afail[k];
-	}
-	if (m > P.cap) {
-		f |= SPF_SEG;           /* (the scatter flagged it too) */
-		m = 0;
-	}
 	/* the bucket's entries (EPT per thread, all in flight): index, seq and
 	 * session, SSRC */
-	uint4 ev4[BP_EPT];
-#pragma unroll
-	for (int j = 0; j < BP_EPT; j++) {
-		const uint32_t k = tid + j * BPB;
-		ev4[j] = k < m ? P.tmp[(size_t)b * P.cap + k]
-			       : make_uint4(0, 0, 0, 0);
-	}
+	uint4 ev4[BK_EPT];
+	uint32_t m;
+	uint32_t f = bk_entries(P.afail, P.n, P.nb, P.bcount, P.tmp, P.cap, &m,
+				ev4);
 	if (tid == 0) {
 		S.bf = 0;
 		S.nlate = S.ndup = 0;
@@ -196,11 +113,11 @@ k_bp_rx_plan(const struct sgpu_bplan_rx R)
 		const uint32_t s = s0 + tid, slot = P.cm[s] >> 1;
 		struct sgpu_sstate x;
 		if (P.upneed && P.upneed[s]) {
-			x = brx_ld(P.up + s);
-			brx_st(P.sst + slot, x);
+			x = bk_ld(P.up + s);
+			bk_st(P.sst + slot, x);
 		}
 		else {
-			x = brx_ld(P.sst + slot);
+			x = bk_ld(P.sst + slot);
 		}
 		S.st[tid] = x;
 		S.cnt[tid] = 0;
@@ -211,7 +128,7 @@ k_bp_rx_plan(const struct sgpu_bplan_rx R)
 	__syncthreads();
 	/* the entries: seq, session, rank in session */
 #pragma unroll
-	for (int j = 0; j < BP_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid + j * BPB;
 		if (k >= m)
 			continue;
@@ -224,31 +141,7 @@ k_bp_rx_plan(const struct sgpu_bplan_rx R)
 		atomicMax(&S.smax[l], ev4[j].z);
 	}
 	__syncthreads();
-	/* segment starts (sessions, <= 256: wave 0) */
-	if (tid < 64) {
-		uint32_t c4[4], v = 0;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			c4[q] = l < ns ? S.cnt[l] : 0u;
-			v += c4[q];
-		}
-		uint32_t x = v;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t y = (uint32_t)__shfl_up((int)x, d);
-			if (tid >= (uint32_t)d)
-				x += y;
-		}
-		uint32_t run = x - v;
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const uint32_t l = 4 * tid + q;
-			if (l < SGPU_BP_NSB)
-				S.start[l] = run;
-			run += c4[q];
-		}
-	}
+	bk_starts(S.cnt, S.start, ns);
 	/* one SSRC per session: the stored one, or the segment's; a window
 	 * the rule's signed arithmetic cannot hold is left to the host */
 	if (tid < ns && S.cnt[tid]) {
@@ -266,30 +159,8 @@ k_bp_rx_plan(const struct sgpu_bplan_rx R)
 	f = 0;
 	__syncthreads();
 	const bool dead = S.bf != 0;    /* the plan fails: nothing more */
-	if (!dead) {
-		/* grouped by session */
-#pragma unroll
-		for (int j = 0; j < BP_EPT; j++) {
-			const uint32_t k = tid + j * BPB;
-			if (k >= m)
-				continue;
-			S.un[S.start[S.sl[k]] + S.srt[k]] = (uint16_t)k;
-		}
-	}
-	__syncthreads();
-	if (!dead) {
-		/* inside a session by packet index: the order the reference
-		 * receives them in */
-		for (uint32_t q = tid; q < m; q += BPB) {
-			const uint32_t e = S.un[q], l = S.sl[e];
-			const uint32_t f0 = S.start[l], c = S.cnt[l];
-			const uint32_t ie = S.ent[e] & BP_IMASK;
-			uint32_t r = 0;
-			for (uint32_t t = f0; t < f0 + c; t++)
-				r += (S.ent[S.un[t]] & BP_IMASK) < ie ? 1u : 0u;
-			S.srt[f0 + r] = (uint16_t)e;
-		}
-	}
+	/* by (session, packet index): the order the reference receives them in */
+	bk_sort16(m, dead, S.ent, S.sl, S.cnt, S.start, S.un, S.srt);
 	__syncthreads();
 	if (tid < ns && !dead && S.cnt[tid]) {
 		/* the receiver's state before the batch as one number; a fresh
@@ -304,11 +175,11 @@ k_bp_rx_plan(const struct sgpu_bplan_rx R)
 	/* the segmented (sum, max) scan over the sorted positions: EPT
 	 * consecutive positions per thread, the threads' aggregates scanned
 	 * across the workgroup */
-	int64_t dv[BP_EPT];
+	int64_t dv[BK_EPT];
 	uint32_t hbits = 0;
 	struct rx_seg agg = rx_seg_identity();
 #pragma unroll
-	for (int j = 0; j < BP_EPT; j++) {
+	for (int j = 0; j < BK_EPT; j++) {
 		const uint32_t k = tid * EPT + j;
 		dv[j] = 0;
 		if (dead || (uint32_t)j >= EPT || k >= m)
@@ -321,9 +192,9 @@ k_bp_rx_plan(const struct sgpu_bplan_rx R)
 		agg = rx_seg_combine(agg, rx_seg_elem(dv[j], head));
 	}
 	{
-		struct rx_seg run = brx_excl_scan(agg, S.wagg);
+		struct rx_seg run = bk_excl_scan(agg, S.wagg);
 #pragma unroll
-		for (int j = 0; j < BP_EPT; j++) {
+		for (int j = 0; j < BK_EPT; j++) {
 			const uint32_t k = tid * EPT + j;
 			if (dead || (uint32_t)j >= EPT || k >= m)
 				continue;
@@ -403,7 +274,7 @@ k_bp_rx_plan(const struct sgpu_bplan_rx R)
 			o.bitmap = rx_bitmap_base(lix, lix0, x.bitmap) |
 				   (uint64_t)S.whi[tid] << 32 | S.wlo[tid];
 		}
-		brx_st(P.sout + s, o);
+		bk_st(P.sout + s, o);
 	}
 	if (tid == 0) {
 		R.cnt[2 * b] = S.nlate;
@@ -459,42 +330,24 @@ k_bp_rx_finish(const struct sgpu_bplan_rx R)
 	if (ok && tid < ns) {
 		/* the touched states replace the resident ones */
 		const uint32_t s = s0 + tid;
-		struct sgpu_sstate o = brx_ld(P.sout + s);
+		struct sgpu_sstate o = bk_ld(P.sout + s);
 		if (o.flags & SST_TOUCHED) {
 			o.flags &= ~(uint32_t)SST_TOUCHED;
-			brx_st(P.sst + (P.cm[s] >> 1), o);
+			bk_st(P.sst + (P.cm[s] >> 1), o);
 		}
 	}
 	if (b != 0)
 		return;
 	/* the call's outcome: the buckets' counts, the miss count next to the
 	 * plan out, all of it to the pinned mirror with vector stores */
-	if (tid < 2)
-		tot[tid] = 0;
-	__syncthreads();
-	{
-		uint32_t a = 0, d = 0;
-		for (uint32_t q = tid; q < P.nb; q += BPB) {
-			a += R.cnt[2 * q];
-			d += R.cnt[2 * q + 1];
-		}
-		if (a)
-			atomicAdd(&tot[0], a);
-		if (d)
-			atomicAdd(&tot[1], d);
-	}
-	__syncthreads();
+	bk_counts(R.cnt, P.nb, tot);
 	if (tid == 0) {
 		R.ro->nlate = tot[0];
 		R.ro->ndup = tot[1];
 		P.out->nfail = nf;
 	}
 	__syncthreads();
-	if (P.outh) {
-		const uint32_t *src = (const uint32_t *)P.out;
-		for (uint32_t w = tid; w < P.outbytes / 4u; w += BPB)
-			P.outh[w] = src[w];
-	}
+	bk_post(P.out, P.outh, P.outbytes, BK_NOWORD, 0);
 }
 
 /* ---- host side ------------------------------------------------------ */
@@ -502,23 +355,10 @@ k_bp_rx_finish(const struct sgpu_bplan_rx R)
 static int brx_check(const struct sgpu_bplan_rx *r)
 {
 	const struct sgpu_bplan *b = &r->b;
-	if (!b->n || b->n > SGPU_BP_NMAX || b->nsess < 2 || !b->nb ||
-	    b->nb > SGPU_BP_NBMAX || b->bshift > 8 || !b->cap ||
-	    b->cap > SGPU_BP_CAPMAX || b->cap % BPB ||
-	    ((uint64_t)b->nb << b->bshift) < b->nsess ||
-	    ((uint64_t)(b->nb - 1) << b->bshift) >= b->nsess ||
+	if (bk_geom_bad(b->n, b->nsess, b->nb, b->bshift, b->cap) ||
 	    b->prot || !r->rs || !r->cnt || !r->ro)
 		return EINVAL;
 	return 0;
-}
-
-static int brx_err(const char *what)
-{
-	const hipError_t e = hipGetLastError();
-	if (e == hipSuccess)
-		return 0;
-	fprintf(stderr, "re_srtp: %s launch: %s\n", what, hipGetErrorString(e));
-	return EIO;
 }
 
 extern "C" int sgpu_bplan_rx_plan(const struct sgpu_bplan_rx *r, void *stream)
@@ -527,7 +367,7 @@ extern "C" int sgpu_bplan_rx_plan(const struct sgpu_bplan_rx *r, void *stream)
 		return EINVAL;
 	hipLaunchKernelGGL(k_bp_rx_plan, dim3(r->b.nb), dim3(BPB), 0,
 			   (hipStream_t)stream, *r);
-	return brx_err("k_bp_rx_plan");
+	return bk_err("k_bp_rx_plan");
 }
 
 extern "C" int sgpu_bplan_rx_finish(const struct sgpu_bplan_rx *r,
@@ -535,9 +375,7 @@ extern "C" int sgpu_bplan_rx_finish(const struct sgpu_bplan_rx *r,
 {
 	if (brx_check(r))
 		return EINVAL;
-	const uint32_t g = (r->b.n + BPB * SGPU_BP_PPT - 1) /
-			   (BPB * SGPU_BP_PPT);
-	hipLaunchKernelGGL(k_bp_rx_finish, dim3(r->b.nb + g), dim3(BPB), 0,
-			   (hipStream_t)stream, *r);
-	return brx_err("k_bp_rx_finish");
+	hipLaunchKernelGGL(k_bp_rx_finish, dim3(r->b.nb + bk_grid(r->b.n)),
+			   dim3(BPB), 0, (hipStream_t)stream, *r);
+	return bk_err("k_bp_rx_finish");
 }
