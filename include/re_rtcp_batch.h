@@ -264,6 +264,62 @@ int rtp_rx_report_host(struct rtp_rx_sess *sessv, size_t nsess,
 		       const uint32_t *local_ssrc,
 		       struct rtcp_enc_msg *rr_msgv);
 
+/* ---- where decoded reports go, and where sender reports come from ------ */
+
+/*
+ * The consumer of rtcp_decode_full_batch_dev's descriptors and items
+ * (libre's rtcp_handler), the transmit statistics, the producer of one SR
+ * or RR struct rtcp_enc_msg per session (mk_sr) and rtcp_stats.
+ * Documented, with struct rtcp_sess_ext, in re_rtcp_sess_batch.h, which
+ * declares them too; repeated here for the same reason.
+ */
+struct rtcp_sess_ext;
+int rtcp_rx_handle_batch_dev(const struct rtcp_desc *descv, uint32_t maxmsg,
+			     const uint32_t *nmsg,
+			     const struct rtcp_item *itemv, uint32_t maxitem,
+			     const uint32_t *nitem, const int32_t *res,
+			     const uint32_t *sess, size_t n,
+			     struct rtp_rx_sess *sessv,
+			     struct rtcp_sess_ext *extv, size_t nsess,
+			     uint64_t recv_ms, uint64_t now_us, int32_t *stat,
+			     void *stream);
+int rtp_tx_stats_batch_dev(const uint8_t *arena, size_t arena_size,
+			   const uint32_t *pos, const uint32_t *end,
+			   const int32_t *res, const uint32_t *sess,
+			   const uint64_t *jfs_rt, size_t n,
+			   struct rtcp_sess_ext *extv, size_t nsess,
+			   int32_t *stat, void *stream);
+int rtcp_tx_report_batch_dev(struct rtp_rx_sess *sessv,
+			     struct rtcp_sess_ext *extv, size_t nsess,
+			     uint64_t now_ms, uint64_t now_us,
+			     struct rtcp_enc_rb *rbv, uint32_t *nrb,
+			     const uint32_t *local_ssrc,
+			     struct rtcp_enc_msg *msgv, void *stream);
+int rtcp_stats_batch_dev(const struct rtp_rx_sess *sessv,
+			 const struct rtcp_sess_ext *extv, size_t nsess,
+			 const uint32_t *sess, const uint32_t *ssrc, size_t n,
+			 uint32_t *out, int32_t *err, void *stream);
+int rtcp_rx_handle_host(const struct rtcp_desc *descv, uint32_t maxmsg,
+			const uint32_t *nmsg, const struct rtcp_item *itemv,
+			uint32_t maxitem, const uint32_t *nitem,
+			const int32_t *res, const uint32_t *sess, size_t n,
+			struct rtp_rx_sess *sessv, struct rtcp_sess_ext *extv,
+			size_t nsess, uint64_t recv_ms, uint64_t now_us,
+			int32_t *stat);
+int rtp_tx_stats_host(const uint8_t *arena, size_t arena_size,
+		      const uint32_t *pos, const uint32_t *end,
+		      const int32_t *res, const uint32_t *sess,
+		      const uint64_t *jfs_rt, size_t n,
+		      struct rtcp_sess_ext *extv, size_t nsess, int32_t *stat);
+int rtcp_tx_report_host(struct rtp_rx_sess *sessv, struct rtcp_sess_ext *extv,
+			size_t nsess, uint64_t now_ms, uint64_t now_us,
+			struct rtcp_enc_rb *rbv, uint32_t *nrb,
+			const uint32_t *local_ssrc, struct rtcp_enc_msg *msgv);
+int rtcp_stats_host(const struct rtp_rx_sess *sessv,
+		    const struct rtcp_sess_ext *extv, size_t nsess,
+		    const uint32_t *sess, const uint32_t *ssrc, size_t n,
+		    uint32_t *out, int32_t *err);
+
 #ifdef __cplusplus
 }
 #endif

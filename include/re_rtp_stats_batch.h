@@ -19,9 +19,10 @@
  * reference's `int` arithmetic is defined the results are the reference's,
  * elsewhere they are still defined.
  *
- * Not covered: the report-block side of incoming reports (handle_rr_block,
- * sess.c:129-142: cum_lost, jit, rtt), the removal of members on BYE, and
- * the transmit statistics (rtcp_sess_tx_rtp).
+ * The report-block side of incoming reports (handle_rr_block,
+ * sess.c:129-142: cum_lost, jit, rtt), the removal of members on BYE, the
+ * transmit statistics (rtcp_sess_tx_rtp), sender reports and rtcp_stats
+ * are in re_rtcp_sess_batch.h.
  */
 #ifndef RE_RTP_STATS_BATCH_H
 #define RE_RTP_STATS_BATCH_H

@@ -32,59 +32,10 @@
 #include <errno.h>
 #include <stdint.h>
 #include <string.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <mutex>
 #include "re_rtp_stats_batch.h"
 #include "../srtpgpu.h"
 #include "rtp_rx_rule.h"
-
-namespace {
-
-constexpr uint32_t RRX_BLOCK = 256;
-constexpr uint32_t RRX_LANES = RTP_RX_MAX_MEMBERS;      /* per session */
-
-static_assert(sizeof(struct rtp_rx_source) == 88 &&
-	      sizeof(struct rtp_rx_sess) == 8 + 8 * 88 &&
-	      sizeof(struct rrx_rec) == 20 && RRX_LANES == 8 &&
-	      RRX_BLOCK % 64 == 0, "layouts of re_rtp_stats_batch.h");
-
-/* the 8 ballot bits of this lane's group */
-__device__ __forceinline__ uint32_t group_ballot(int pred)
-{
-	const uint32_t lane = threadIdx.x & 63;
-	return (uint32_t)(__ballot(pred) >> (lane & ~7u)) & 0xffu;
-}
-
-/* first index in keys[0 .. n) (ascending) with keys[i] >= v */
-__device__ __forceinline__ uint32_t lower_bound(const uint32_t *keys,
-						uint32_t n, uint32_t v)
-{
-	uint32_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint32_t mid = lo + (hi - lo) / 2;
-		if (keys[mid] < v)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-/* a session's run [lo, hi) of the grouped order; no keys: one run, s = 0 */
-__device__ __forceinline__ void run_of(const uint32_t *keys, uint32_t n,
-				       uint32_t s, uint32_t &lo, uint32_t &hi)
-{
-	if (keys) {
-		lo = lower_bound(keys, n, s);
-		hi = lower_bound(keys, n, s + 1);
-	}
-	else {
-		lo = 0;
-		hi = s ? 0 : n;
-	}
-}
-
-} /* namespace */
+#include "rtp_stats_common.h"
 
 /* one lane per packet: window, header, record, key, index, final stats */
 __global__ void k_rrx_record(const uint8_t *__restrict__ arena, uint64_t asz,
@@ -301,30 +252,16 @@ __global__ void k_rrx_report(struct rtp_rx_sess *__restrict__ sessv,
 
 /* ---- host side ---------------------------------------------------------- */
 
-namespace {
+std::mutex rrx_mu;
+static struct rrx_scratch g_scr[16];
 
-struct scratch {
-	void *p;
-	size_t size;
-	hipEvent_t ev;          /* after the last use */
-	bool used;
-};
-
-std::mutex g_mu;
-struct scratch g_scr[16];
-
-size_t al(size_t x)
-{
-	return (x + 255) & ~(size_t)255;
-}
-
-/* with g_mu held: >= bytes of scratch, ordered behind its last use */
-int scratch_get(size_t bytes, hipStream_t st, struct scratch **sp)
+/* with rrx_mu held: >= bytes of scratch, ordered behind its last use */
+int rrx_scratch_get(size_t bytes, hipStream_t st, struct rrx_scratch **sp)
 {
 	int dev = 0;
 	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16)
 		return EIO;
-	struct scratch *sc = &g_scr[dev];
+	struct rrx_scratch *sc = &g_scr[dev];
 	if (!sc->ev &&
 	    hipEventCreateWithFlags(&sc->ev, hipEventDisableTiming) != hipSuccess)
 		return EIO;
@@ -348,35 +285,13 @@ int scratch_get(size_t bytes, hipStream_t st, struct scratch **sp)
 	return 0;
 }
 
-int scratch_put(struct scratch *sc, hipStream_t st)
+int rrx_scratch_put(struct rrx_scratch *sc, hipStream_t st)
 {
 	sc->used = true;
 	return hipEventRecord(sc->ev, st) == hipSuccess ? 0 : EIO;
 }
 
-uint32_t key_bits(uint32_t nsess)
-{
-	uint32_t b = 1;
-	while (b < 32 && (nsess >> b))
-		b++;
-	return b;
-}
-
-size_t sort_bytes(uint32_t n, uint32_t bits)
-{
-	size_t tb = 0;
-	(void)rocprim::radix_sort_pairs((void *)NULL, tb,
-					(const uint32_t *)NULL,
-					(uint32_t *)NULL,
-					(const uint32_t *)NULL,
-					(uint32_t *)NULL, n, 0, bits);
-	return tb ? tb : 1;
-}
-
-uint32_t blocks(uint64_t threads)
-{
-	return (uint32_t)((threads + RRX_BLOCK - 1) / RRX_BLOCK);
-}
+namespace {
 
 /* the scratch of a call over n items: records (stats only), then the
  * grouping's four arrays and the sort's storage */
@@ -419,9 +334,9 @@ extern "C" int sgpu_rtp_rx_stats(const uint8_t *arena, uint64_t arena_size,
 	hipStream_t st = (hipStream_t)stream;
 	const uint32_t bits = key_bits(nsess);
 	const struct layout l = lay(n, true, sess != NULL, bits);
-	std::lock_guard<std::mutex> g(g_mu);
-	struct scratch *sc;
-	int err = scratch_get(l.total, st, &sc);
+	std::lock_guard<std::mutex> g(rrx_mu);
+	struct rrx_scratch *sc;
+	int err = rrx_scratch_get(l.total, st, &sc);
 	if (err)
 		return err;
 	uint8_t *b = (uint8_t *)sc->p;
@@ -452,7 +367,7 @@ extern "C" int sgpu_rtp_rx_stats(const uint8_t *arena, uint64_t arena_size,
 				   stat);
 	if (hipGetLastError() != hipSuccess)
 		err = EIO;
-	if (scratch_put(sc, st) && !err)
+	if (rrx_scratch_put(sc, st) && !err)
 		err = EIO;
 	return err;
 }
@@ -467,13 +382,13 @@ extern "C" int sgpu_rtp_rx_sr(struct rtp_rx_sess *sessv, uint32_t nsess,
 	hipStream_t st = (hipStream_t)stream;
 	const uint32_t bits = key_bits(nsess);
 	uint32_t *kout = NULL, *vout = NULL;
-	struct scratch *sc = NULL;
+	struct rrx_scratch *sc = NULL;
 	int err = 0;
-	std::unique_lock<std::mutex> g(g_mu, std::defer_lock);
+	std::unique_lock<std::mutex> g(rrx_mu, std::defer_lock);
 	if (sess) {
 		const struct layout l = lay(n, false, true, bits);
 		g.lock();
-		err = scratch_get(l.total, st, &sc);
+		err = rrx_scratch_get(l.total, st, &sc);
 		if (err)
 			return err;
 		uint8_t *b = (uint8_t *)sc->p;
@@ -498,7 +413,7 @@ extern "C" int sgpu_rtp_rx_sr(struct rtp_rx_sess *sessv, uint32_t nsess,
 				   ntp_frac, rtp_ts, psent, osent, recv_ms, n);
 	if (hipGetLastError() != hipSuccess)
 		err = EIO;
-	if (sc && scratch_put(sc, st) && !err)
+	if (sc && rrx_scratch_put(sc, st) && !err)
 		err = EIO;
 	return err;
 }

@@ -1307,6 +1307,32 @@ int sgpu_rtp_rx_report(struct rtp_rx_sess *sessv, uint32_t nsess,
 		       uint64_t now_ms, struct rtcp_enc_rb *rbv, uint32_t *nrb,
 		       const uint32_t *local_ssrc, struct rtcp_enc_msg *rr_msgv,
 		       void *stream);
+/* rtcp_sess.hip: RTCP session state (re_rtcp_sess_batch.h); a_compact /
+ * ntp_hi / ntp_lo: the call's wall clock as NTP time, from the host */
+struct rtcp_sess_ext;
+int sgpu_rtcp_rx_handle(const struct rtcp_desc *descv, uint32_t maxmsg,
+			const uint32_t *nmsg, const struct rtcp_item *itemv,
+			uint32_t maxitem, const uint32_t *nitem,
+			const int32_t *res, const uint32_t *sess, uint32_t n,
+			struct rtp_rx_sess *sessv, struct rtcp_sess_ext *extv,
+			uint32_t nsess, uint64_t recv_ms, uint32_t a_compact,
+			int32_t *stat, void *stream);
+int sgpu_rtp_tx_stats(const uint8_t *arena, uint64_t arena_size,
+		      const uint32_t *pos, const uint32_t *end,
+		      const int32_t *res, const uint32_t *sess,
+		      const uint64_t *jfs_rt, uint32_t n,
+		      struct rtcp_sess_ext *extv, uint32_t nsess, int32_t *stat,
+		      void *stream);
+int sgpu_rtcp_tx_report(struct rtp_rx_sess *sessv, struct rtcp_sess_ext *extv,
+			uint32_t nsess, uint64_t now_ms, uint64_t now_us,
+			uint32_t ntp_hi, uint32_t ntp_lo,
+			struct rtcp_enc_rb *rbv, uint32_t *nrb,
+			const uint32_t *local_ssrc, struct rtcp_enc_msg *msgv,
+			void *stream);
+int sgpu_rtcp_stats(const struct rtp_rx_sess *sessv,
+		    const struct rtcp_sess_ext *extv, uint32_t nsess,
+		    const uint32_t *sess, const uint32_t *ssrc, uint32_t n,
+		    uint32_t *out, int32_t *err, void *stream);
 
 #define SGPU_PROF_NAME 48
 void  sgpu_prof_read(double *ms, uint64_t *launches, uint64_t *jobs,

@@ -121,6 +121,10 @@ EXPORTS = (
     "rtcp_decode_batch_dev",
     "rtp_rx_stats_batch_dev", "rtp_rx_sr_batch_dev", "rtp_rx_report_batch_dev",
     "rtp_rx_stats_host", "rtp_rx_sr_host", "rtp_rx_report_host",
+    "rtcp_rx_handle_batch_dev", "rtp_tx_stats_batch_dev",
+    "rtcp_tx_report_batch_dev", "rtcp_stats_batch_dev",
+    "rtcp_rx_handle_host", "rtp_tx_stats_host", "rtcp_tx_report_host",
+    "rtcp_stats_host",
     "srtp_udp_alloc", "srtp_udp_recv", "srtp_udp_send", "srtp_udp_stats",
     "srtp_udp_pipeline", "srtp_udp_times",
     "srtp_dtls_key_size", "srtp_keyinfo_split", "srtp_dtls_keying_many",
@@ -205,6 +209,19 @@ def load():
     L.rtp_rx_sr_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, u64, sz]
     L.rtp_rx_report_batch_dev.argtypes = [vp, sz, u64, vp, vp, vp, vp, vp]
     L.rtp_rx_report_host.argtypes = [vp, sz, u64, vp, vp, vp, vp]
+    u32 = ctypes.c_uint32
+    L.rtcp_rx_handle_host.argtypes = [vp, u32, vp, vp, u32, vp, vp, vp, sz,
+                                      vp, vp, sz, u64, u64, vp]
+    L.rtcp_rx_handle_batch_dev.argtypes = \
+        L.rtcp_rx_handle_host.argtypes + [vp]
+    L.rtp_tx_stats_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, sz,
+                                    vp]
+    L.rtp_tx_stats_batch_dev.argtypes = L.rtp_tx_stats_host.argtypes + [vp]
+    L.rtcp_tx_report_host.argtypes = [vp, vp, sz, u64, u64, vp, vp, vp, vp]
+    L.rtcp_tx_report_batch_dev.argtypes = \
+        L.rtcp_tx_report_host.argtypes + [vp]
+    L.rtcp_stats_host.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
+    L.rtcp_stats_batch_dev.argtypes = L.rtcp_stats_host.argtypes + [vp]
     L.srtp_udp_alloc.argtypes = [ctypes.POINTER(vp), ctypes.c_int, vp, vp,
                                  sz, sz, UDP_RECV_H, vp]
     L.srtp_udp_recv.argtypes = [vp, ctypes.c_int]
@@ -635,6 +652,83 @@ def rtp_rx_report(sessv_ptr, nsess, now_ms, rbv_ptr, nrb_ptr,
     return lib().rtp_rx_report_batch_dev(sessv_ptr, nsess, now_ms, rbv_ptr,
                                          nrb_ptr, local_ssrc_ptr,
                                          rr_msgv_ptr, stream)
+
+
+# ---- RTCP session state (include/re_rtcp_sess_batch.h) ------------------
+RTCP_RX_TRUNCATED = -4
+
+
+def rtcp_sess_ext_dtype():
+    """numpy layout of struct rtcp_sess_ext (128 bytes); all zero is a
+    fresh session"""
+    import numpy as np
+    ext = np.dtype([("cum_lost", "<i4", (8,)), ("jit", "<u4", (8,)),
+                    ("rtt", "<u4", (8,)), ("psent", "<u4"), ("osent", "<u4"),
+                    ("jfs_rt_ref", "<u8"), ("ts_ref", "<u4"),
+                    ("ts_synced", "<u4"), ("srate_tx", "<u4"),
+                    ("srate_rx", "<u4")])
+    assert ext.itemsize == 128
+    return ext
+
+
+def rtcp_rx_handle(desc_ptr, maxmsg, nmsg_ptr, item_ptr, maxitem, nitem_ptr,
+                   res_ptr, sess_ptr, n, sessv_ptr, extv_ptr, nsess, recv_ms,
+                   now_us, stat_ptr, stream=None, host=False):
+    """rtcp_rx_handle_batch_dev over rtcp_decode_full_dev's device arrays
+    (host=True: rtcp_rx_handle_host over host arrays); returns rc"""
+    a = (desc_ptr, maxmsg, nmsg_ptr, item_ptr, maxitem, nitem_ptr, res_ptr,
+         sess_ptr, n, sessv_ptr, extv_ptr, nsess, recv_ms, now_us, stat_ptr)
+    if host:
+        return lib().rtcp_rx_handle_host(*a)
+    return lib().rtcp_rx_handle_batch_dev(*a, stream)
+
+
+def rtp_tx_stats(arena_ptr, arena_size, pos_ptr, end_ptr, res_ptr, sess_ptr,
+                 jfs_rt_ptr, n, extv_ptr, nsess, stat_ptr, stream=None,
+                 host=False):
+    """rtp_tx_stats_batch_dev / rtp_tx_stats_host; returns rc"""
+    a = (arena_ptr, arena_size, pos_ptr, end_ptr, res_ptr, sess_ptr,
+         jfs_rt_ptr, n, extv_ptr, nsess, stat_ptr)
+    if host:
+        return lib().rtp_tx_stats_host(*a)
+    return lib().rtp_tx_stats_batch_dev(*a, stream)
+
+
+def rtcp_tx_report(sessv_ptr, extv_ptr, nsess, now_ms, now_us, rbv_ptr,
+                   nrb_ptr, local_ssrc_ptr, msgv_ptr, stream=None,
+                   host=False):
+    """rtcp_tx_report_batch_dev / rtcp_tx_report_host: rbv holds nsess * 8
+    struct rtcp_enc_rb, msgv nsess struct rtcp_enc_msg (SR or RR); returns
+    rc"""
+    a = (sessv_ptr, extv_ptr, nsess, now_ms, now_us, rbv_ptr, nrb_ptr,
+         local_ssrc_ptr, msgv_ptr)
+    if host:
+        return lib().rtcp_tx_report_host(*a)
+    return lib().rtcp_tx_report_batch_dev(*a, stream)
+
+
+def rtcp_stats(sessv_ptr, extv_ptr, nsess, sess_ptr, ssrc_ptr, n, out_ptr,
+               err_ptr, stream=None, host=False):
+    """rtcp_stats_batch_dev / rtcp_stats_host: out holds n rows of seven
+    uint32 (tx_sent, tx_lost, tx_jit, rx_sent, rx_lost, rx_jit, rtt), err n
+    int32; returns rc"""
+    a = (sessv_ptr, extv_ptr, nsess, sess_ptr, ssrc_ptr, n, out_ptr, err_ptr)
+    if host:
+        return lib().rtcp_stats_host(*a)
+    return lib().rtcp_stats_batch_dev(*a, stream)
+
+
+def rtcp_dec_dtypes():
+    """numpy layouts of struct rtcp_desc (20 bytes) and struct rtcp_item
+    (32 bytes), rtcp_decode_full_dev's outputs"""
+    import numpy as np
+    desc = np.dtype([("off", "<u4"), ("size", "<u4"), ("pt", "u1"),
+                     ("count", "u1"), ("length", "<u2"), ("ssrc", "<u4"),
+                     ("aux", "<u4")])
+    item = np.dtype([("msg", "<u2"), ("kind", "u1"), ("sub", "u1"),
+                     ("v", "<u4", (7,))])
+    assert desc.itemsize == 20 and item.itemsize == 32
+    return desc, item
 
 
 def rtcp_decode_full_dev(arena_ptr, arena_size, pos_ptr, end_ptr, n,
